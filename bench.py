@@ -16,6 +16,12 @@ W untimed warm-up steps, then K timed steps bracketed by barrier + device sync; 
 slowest rank's time is used; rank 0 prints ONE JSON line with the whole-job value.
 The reference publishes no throughput, so vs_baseline is null.
 
+A plain run does what that figure needs and no more: set-up, warm-up, the K timed steps, the line.
+``--full`` adds the measurements that take steps of their own after the timed region (``step_spread``,
+``phases_ms``; both null without it).  ``--dump-outputs DIR`` writes the last timed step's losses and
+both models' parameters as ``DIR/<name>.npy``; such a run keeps the fixed replay plan (``replay_plan``
+in the line), so its steps and batches -- and the files -- are a function of the arguments alone.
+
 ``python bench.py --gpus N`` (N > 1) without a torchrun environment starts the N ranks itself
 (one child process per GPU through parallel/launch.py, BEFORE this process imports torch or
 touches a GPU), relays rank 0's JSON line on stdout and exits non-zero if any rank fails.  Under
@@ -49,6 +55,15 @@ def main() -> int:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, on extra steps after the timed region: "
+                         "the event-timed windows (--spread-windows: step_spread) and, N > 1, the per-phase times "
+                         "(--phase-steps: phases_ms).  Off: both are skipped and reported as null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them left a caller -- the two losses and both "
+                         "models' parameters -- as DIR/<name>.npy (float32; rank 0's at N > 1).  The replay plan is then "
+                         "the fixed one, not the one calibrated from this run's measured rates, so the same arguments "
+                         "train the same steps on the same batches in every run")
     ap.add_argument("--batch", type=int, default=256, help="per-stream batch (batch_size_DML)")
     ap.add_argument("--qubits", type=int, default=8)
     ap.add_argument("--pilot", type=int, default=128, choices=[128, 256], help="Pilot_num (P128 / P256 configs)")
@@ -79,7 +94,7 @@ def main() -> int:
     ap.add_argument("--dp-one-graph", action="store_true",
                     help="DP plan: capture the whole step, RCCL collectives included, in one HIP graph")
     ap.add_argument("--phase-steps", type=int, default=20,
-                    help="N > 1: extra steps (after the timed region) timed per phase with HIP events; 0 = off")
+                    help="--full, N > 1: extra steps (after the timed region) timed per phase with HIP events; 0 = off")
     ap.add_argument("--dp-qsc", default="auto", choices=["auto", "g2", "fwd", "indep"],
                     help="N > 1, one-graph DP plan: the QSC branch beside the conv backward (g2), forked after the "
                          "gather (fwd), or an independent chain with its own bucket (indep, all-reduce plan); auto = "
@@ -99,7 +114,7 @@ def main() -> int:
     ap.add_argument("--gemm-cfg", default=None,
                     help="FC GEMM tile configurations 'fwd,wgrad,dgrad' (knobs.KNOBS.gemm_cfg; default: the shipped ones)")
     ap.add_argument("--spread-windows", type=int, default=8,
-                    help="extra event-timed windows after the timed region (step_spread in the JSON line); 0 = off")
+                    help="--full: extra event-timed windows after the timed region (step_spread in the JSON line); 0 = off")
     ap.add_argument("--stream-mode", default="indep", choices=["serial", "dagq", "indep"],
                     help="how the step's independent branches run (FlagshipTrainer): one chain, or the QSC branch "
                          "forked off the HDCE chain")
@@ -210,7 +225,10 @@ def main() -> int:
             sync()
             # the replay plan from this box's measured rates: GPU seconds per step (this settle run, 5 % margin) and
             # the host's submission cost (fitted over the replays so far) -- FlagshipTrainer._reps_calibrated
-            tr.calibrate(0.95 * (time.perf_counter() - t0) / ns)
+            # (not with --dump-outputs: measured rates differ from run to run, and with them the plan, the number
+            # of warm-up replays and where the epochs wrap -- the dumped state must depend on the arguments alone)
+            if not args.dump_outputs:
+                tr.calibrate(0.95 * (time.perf_counter() - t0) / ns)
             warm(tr, n)
         sync()
         ctx.barrier()
@@ -272,12 +290,14 @@ def main() -> int:
     k = tr._k()
     settle = (max(0, args.settle_steps) + k - 1) // k * k
     elapsed, host = timed(tr, args.steps, settle)
+    if args.dump_outputs and ctx.is_main:
+        dump_outputs(args.dump_outputs, tr)
 
     # spread: after the timed window, 8 more windows of `steps_per_graph` steps each timed with HIP events (no
     # host sync inside a window; the max over ranks per window) -- the run-to-run spread the single timed window
     # cannot show
     spread = None
-    if ctx.device.type == "cuda" and args.spread_windows > 0:
+    if args.full and ctx.device.type == "cuda" and args.spread_windows > 0:
         k = tr._k()
         warm(tr, k)   # (the windows' graph sets captured and warmed outside them)
         evs = []
@@ -302,7 +322,7 @@ def main() -> int:
     value = samples / elapsed
     dp = len(tr.graphs) == 5 or (one_graph and (ctx.world > 1 or cfg.split_graphs))
     phases = None
-    if args.phase_steps > 0 and dp:
+    if args.full and args.phase_steps > 0 and dp:
         phases = tr.phase_times(args.phase_steps)
     if phases is not None:
         keys = sorted(phases)
@@ -320,6 +340,7 @@ def main() -> int:
             "lead_in": args.lead_in,
             "ramp": args.ramp,
             "replays": tr._reps(args.steps),
+            "replay_plan": "calibrated" if getattr(tr, "_g_est", None) else "fixed",
             # (the calibrated plan's inputs: host submit ms = a + c * steps, GPU ms per step)
             "replay_rates_ms": {"submit_a": round(1e3 * tr._sub_est[0], 4), "submit_c": round(1e3 * tr._sub_est[1], 4),
                                 "gpu": round(1e3 * tr._g_est, 4)} if getattr(tr, "_g_est", None) else None,
@@ -387,6 +408,31 @@ def main() -> int:
     tr.close()
     shutdown()
     return 0
+
+
+DUMP_BYTES = 60 * 10 ** 6   # (--dump-outputs: all files together stay under 64 MB)
+
+
+def dump_outputs(dest: str, tr) -> None:
+    """Write what the last timed step left a caller of ``FlagshipTrainer.run`` as ``dest/<name>.npy`` (float32): the
+    step's two losses and both models' parameters after its update.  An array that does not fit what is left of
+    DUMP_BYTES is written as a fixed sample: its elements at sorted indices drawn with seed 0 (the same indices
+    for the same array length)."""
+    import numpy as np
+    import torch
+
+    arrays = {"hdce_loss": tr.hloss, "qsc_loss": tr.qloss,
+              "qsc_params": tr.qspace.flat[:tr.qspace.extra_off], "hdce_params": tr.hdce.space.flat[:tr.hdce.space.extra_off]}
+    os.makedirs(dest, exist_ok=True)
+    left = DUMP_BYTES
+    for name, t in arrays.items():   # (the small ones first: only the estimator's parameters can need sampling)
+        t = t.detach().reshape(-1)
+        if t.numel() * 4 > left:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), size=left // 4))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float32).cpu().numpy()
+        left -= a.nbytes
+        np.save(os.path.join(dest, name + ".npy"), a)
 
 
 def supervise(argv, args) -> int:

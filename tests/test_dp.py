@@ -104,6 +104,31 @@ def test_bench_supervisor_falls_back_when_a_rank_fails():
     assert recs[0]["config"]["dp_graph"] == "five"
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and leaves the extra measurements (`--full`) out;
+    `--dump-outputs DIR` writes the last step's losses and parameters as float32 .npy files, the same in
+    every run with the same arguments, under 64 MB together."""
+    import numpy as np
+    dumps = []
+    for d in ("a", "b"):
+        rc, recs, err = _bench(["--gpus", "1"] + SMALL + ["--settle-steps", "4", "--dump-outputs", str(tmp_path / d)])
+        assert rc == 0, err[-2000:]
+        assert len(recs) == 1, recs
+        r = recs[0]
+        assert r["steps"] == 2 and sum(r["replays"]) == 2 and r["ms_per_step"] > 0
+        assert r["step_spread"] is None and r["replay_plan"] == "fixed"
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert key in r
+        dumps.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = dumps
+    assert sorted(a) == ["hdce_loss.npy", "hdce_params.npy", "qsc_loss.npy", "qsc_params.npy"]
+    assert sum(v.nbytes for v in a.values()) <= 64 * 10 ** 6
+    for f in a:
+        assert a[f].dtype == np.float32 and np.isfinite(a[f]).all()
+        assert np.array_equal(a[f], b[f]), f
+    assert a["hdce_loss.npy"].shape == (2,) and a["qsc_loss.npy"].shape == (1,)
+
+
 def test_bench_world_mismatch_is_an_error():
     rc, recs, err = _bench(["--gpus", "2"] + SMALL, env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert rc != 0 and not recs

@@ -210,7 +210,7 @@ def test_bench_two_ranks_one_gpu_reports_phases(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update({"QDML_DIST_BACKEND": "gloo", "OMP_NUM_THREADS": "2"})
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                        "--phase-steps", "3"], capture_output=True, text=True, env=env, timeout=300, cwd=root)
+                        "--full", "--phase-steps", "3"], capture_output=True, text=True, env=env, timeout=300, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     recs = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(recs) == 1
