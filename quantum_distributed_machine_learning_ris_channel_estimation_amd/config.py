@@ -115,6 +115,8 @@ class EvalConfig:
     bn_adapt: bool = False
     # the HDCE checkpoint tag to evaluate ("": the classifiers' epoch tag; "swa": RunnerConfig.swa_epochs' average)
     hdce_tag: str = ""
+    # measurement shots per sample of the quantum SC's circuit (0: exact expectation values; ops/quantum.py qsim)
+    qsc_shots: int = 0
 
     def update_from_dict(self, d: Dict[str, Any]) -> "EvalConfig":
         names = {f.name for f in dataclasses.fields(self)}

@@ -8,6 +8,7 @@
 // Wire i <-> bit i of the basis index.  Backward is adjoint differentiation over the
 // explicit gate list; per-sample weight gradients are summed in sample order so the
 // result is deterministic for any thread count.
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstdint>
@@ -143,6 +144,77 @@ QD_API int qd_cpu_qsim_bwd(const float* x, const float* w, const float* gE, floa
     double t = 0;
     for (int b = 0; b < B; ++b) t += per[(size_t)b * P + p];
     dw[p] = (float)t;
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------- finite shots
+// probs (B, 2^n) double = |amp_k|^2 of the final state, natural basis order (the oracle of qd_qsim_probs).
+QD_API int qd_cpu_qsim_probs(const float* x, const float* w, double* probs, int B, int n, int L) {
+  if (n < 1 || n > 24) return 1;
+  const size_t D = size_t(1) << n;
+#pragma omp parallel for schedule(static)
+  for (int b = 0; b < B; ++b) {
+    std::vector<cd> s(D);
+    forward_state(s, build_circuit(x + (size_t)b * n, w, n, L));
+    for (size_t k = 0; k < D; ++k) probs[(size_t)b * D + k] = std::norm(s[k]);
+  }
+  return 0;
+}
+
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11).
+QD_API void qd_cpu_philox4x32(const uint32_t* ctr4, const uint32_t* key2, uint32_t* out4) {
+  uint32_t c0 = ctr4[0], c1 = ctr4[1], c2 = ctr4[2], c3 = ctr4[3], k0 = key2[0], k1 = key2[1];
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out4[0] = c0;
+  out4[1] = c1;
+  out4[2] = c2;
+  out4[3] = c3;
+}
+
+// Finite-shot <Z_i> from fp32 probabilities, sequentially: the sampling contract of csrc/hip/qsim_shots.hip (see its
+// header), bit for bit.  probs (B, 2^n) fp32, a normalised distribution; E (B, n) fp32; counts (B, n) int32, nullable.
+QD_API int qd_cpu_sample_z(const float* probs, float* E, int32_t* counts, int B, int n, int shots, uint64_t seed,
+                           uint64_t ctr) {
+  if (n < 2 || n > 12 || shots < 1 || shots > (1 << 20)) return 1;
+  const size_t D = size_t(1) << n;
+  const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+#pragma omp parallel for schedule(static)
+  for (int b = 0; b < B; ++b) {
+    std::vector<uint32_t> cum(D);
+    uint32_t run = 0;
+    for (size_t k = 0; k < D; ++k) {
+      const float p = probs[(size_t)b * D + k];
+      run += p > 0.f ? (uint32_t)std::nearbyintf(p * 1073741824.f) : 0u;   // (default rounding mode: to nearest even)
+      cum[k] = run;
+    }
+    const uint32_t T = run;
+    std::vector<int32_t> c1(n, 0);
+    uint32_t rnd[4] = {0, 0, 0, 0};
+    for (int s = 0; s < shots; ++s) {
+      if ((s & 3) == 0) {
+        const uint32_t c4[4] = {(uint32_t)s >> 2, (uint32_t)b, (uint32_t)ctr, (uint32_t)(ctr >> 32)};
+        qd_cpu_philox4x32(c4, key, rnd);
+      }
+      const uint32_t t = (uint32_t)(((uint64_t)rnd[s & 3] * T) >> 32);
+      // the smallest index with cum[k] > t (exists whenever T > 0; an all-zero row gives D - 1)
+      size_t k = std::upper_bound(cum.begin(), cum.end(), t) - cum.begin();
+      if (k > D - 1) k = D - 1;
+      for (int i = 0; i < n; ++i) c1[i] += (int32_t)((k >> i) & 1);
+    }
+    for (int i = 0; i < n; ++i) {
+      E[(size_t)b * n + i] = (float)(shots - 2 * c1[i]) / (float)shots;
+      if (counts != nullptr) counts[(size_t)b * n + i] = c1[i];
+    }
   }
   return 0;
 }

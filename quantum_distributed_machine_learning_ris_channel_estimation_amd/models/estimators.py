@@ -77,20 +77,39 @@ class SC_P128(nn.Module):
 
 class QuantumLayer(nn.Module):
     """Drop-in for PennyLane's ``qml.qnn.TorchLayer`` (E:144-149): owns ``weights``
-    of shape (n_layers, n_qubits, 2), maps (B, n) angles to (B, n) <Z_i> values."""
+    of shape (n_layers, n_qubits, 2), maps (B, n) angles to (B, n) <Z_i> values.
 
-    def __init__(self, n_qubits: int, n_layers: int, backend: Optional[str] = None):
+    ``shots`` (settable; None / 0 = exact expectations) is the device's ``shots=``: every <Z_i> is then
+    estimated from that many measurement shots (ops/quantum.py ``qsim(shots=)``; gradients stay exact,
+    straight-through).  The shot stream is keyed by ``shot_seed`` and a Python-side call counter that
+    every forward advances, so successive calls draw different shots; ``manual_shot_seed`` restarts it.
+    Neither is a parameter or a buffer: the state_dict is that of the exact layer."""
+
+    def __init__(self, n_qubits: int, n_layers: int, backend: Optional[str] = None, shots: Optional[int] = None):
         super().__init__()
         self.n_qubits, self.n_layers = n_qubits, n_layers
         self.backend = backend
+        self.shots = shots
+        self.shot_seed = 0
+        self._shot_calls = 0
         self.weights = nn.Parameter(init_weights_(torch.empty(n_layers, n_qubits, 2)))
+
+    def manual_shot_seed(self, seed: int) -> None:
+        """Seed the shot stream and restart its call counter."""
+        self.shot_seed = int(seed)
+        self._shot_calls = 0
 
     def forward(self, x: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         w = self.weights if weights is None else weights
-        return qsim(x.float(), w, self.backend)
+        if not self.shots:
+            return qsim(x.float(), w, self.backend)
+        call = self._shot_calls
+        self._shot_calls += 1
+        return qsim(x.float(), w, self.backend, shots=int(self.shots), seed=self.shot_seed, counter=call)
 
     def extra_repr(self) -> str:
-        return f"n_qubits={self.n_qubits}, n_layers={self.n_layers}, backend={self.backend}"
+        return (f"n_qubits={self.n_qubits}, n_layers={self.n_layers}, backend={self.backend}, shots={self.shots}, "
+                f"shot_seed={self.shot_seed}")
 
 
 class QSC_P128(nn.Module):
@@ -108,11 +127,13 @@ class QSC_P128(nn.Module):
     ``use_quantum=False`` selects ``classical_fallback`` (referenced at E:168-170 but never
     defined there): Linear(n, n) + Tanh in place of the VQC, an equal-width classical ablation
     with the same (-1, 1) output range as <Z_i>.
+    ``shots`` goes to the ``qlayer`` (finite-shot <Z_i>; None = exact).
     """
 
     def __init__(self, n_qubits: int = 6, n_layers: int = 3, n_classes: int = 3, use_quantumnat: bool = True,
                  use_gradient_pruning: bool = True, pilot_num: int = 128, backend: Optional[str] = None,
-                 noise_level: float = 0.01, gradient_threshold: float = 0.1, use_quantum: bool = True):
+                 noise_level: float = 0.01, gradient_threshold: float = 0.1, use_quantum: bool = True,
+                 shots: Optional[int] = None):
         super().__init__()
         self.use_quantum = use_quantum
         self.num_qubits = n_qubits
@@ -126,7 +147,7 @@ class QSC_P128(nn.Module):
         H, W = pilot_grid(pilot_num)
         flat = 32 * (H // 4) * (W // 4)
         # registration order matters: qlayer.weights is the first state_dict key (E:149 < E:152)
-        self.qlayer = QuantumLayer(n_qubits, n_layers, backend)
+        self.qlayer = QuantumLayer(n_qubits, n_layers, backend, shots)
         self.preprocess = nn.Sequential(
             nn.Conv2d(2, 16, kernel_size=3, stride=1, padding=1),
             nn.ReLU(),

@@ -285,20 +285,28 @@ class QSCStepHIP:
 
     @torch.no_grad()
     def infer(self, x: torch.Tensor, pred: Optional[torch.Tensor] = None,
-              logp: Optional[torch.Tensor] = None) -> None:
+              logp: Optional[torch.Tensor] = None, shots: int = 0, seed: int = 0, counter=0) -> None:
         """Inference on the HIP kernels (x.shape[0] == B): preprocess CNN, the circuit with the clean
         master weights (no QuantumNAT noise), then a thread-per-sample head -> log-probabilities (B, C)
-        and / or the argmax (B,) int64."""
+        and / or the argmax (B,) int64.  ``shots`` > 0: the circuit's <Z_i> are finite-shot estimates
+        (csrc/hip/qsim_shots.hip's fused kernel on the angles, n <= 12; ``seed`` / ``counter`` as in
+        ops.quantum.qsim)."""
         m = self.m
         B, n, L = self.B, self.n, self.L
         assert x.shape[0] == B and x.is_contiguous() and self.impl == "mfma"
         st = nat.stream_ptr(x.device)
         self._fwd_mfma(x, self.space.flat, st)
         w = m.qlayer.weights.detach().contiguous()
-        extra = (nat.ptr(self.qws) if self.qws is not None else None,
-                 nat.ptr(self.psave) if self.psave is not None else None) if self.big else \
-            (nat.ptr(self.psave) if self.psave is not None else None,)
-        nat.check(self._qf(nat.ptr(self.angles), nat.ptr(w), nat.ptr(self.E), B, n, L, 0, *extra, st), "qsim_fwd")
+        if shots:
+            from . import quantum as Q
+            Q._hip_shots_limit(n)
+            ctr0, cptr = Q._split_counter(counter, x.device)
+            Q.hip_qsim_shots_fwd(self.angles, w, self.E, None, Q._check_shots(shots), int(seed), ctr0, cptr)
+        else:
+            extra = (nat.ptr(self.qws) if self.qws is not None else None,
+                     nat.ptr(self.psave) if self.psave is not None else None) if self.big else \
+                (nat.ptr(self.psave) if self.psave is not None else None,)
+            nat.check(self._qf(nat.ptr(self.angles), nat.ptr(w), nat.ptr(self.E), B, n, L, 0, *extra, st), "qsim_fwd")
         cls = m.classifier
         f = nat.fn(nat.hip_lib(), "qd_qsc_infer_head", [_p, _p, _p, _p, _p, _i, _i, _i, _p])
         nat.check(f(nat.ptr(self.E), nat.ptr(cls.weight), nat.ptr(cls.bias), nat.ptr(logp) if logp is not None else None,

@@ -16,6 +16,10 @@ Here three interchangeable backends implement the SAME function:
 * ``torch`` -- eager complex-tensor simulator differentiated by autograd: the
                "reference-equivalent" gate-by-gate path used as a baseline and an
                oracle.  Never selected implicitly on a GPU.
+
+Finite shots (``qsim(..., shots=N)``, ``qsim_probs``, ``sample_z``, ``counter_add``): <Z_i> estimated from N
+measurement shots of the final state -- csrc/hip/qsim_shots.hip (n <= 12) on ``hip``, simulate-then-sample on
+``cpu`` with the same integer sampling contract; gradients stay the exact adjoint (straight-through).
 """
 from __future__ import annotations
 
@@ -200,8 +204,9 @@ def z_signs(n: int, device=None, dtype=torch.float32) -> torch.Tensor:
     return (1 - 2 * bits).to(dtype)
 
 
-def qsim_torch(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    """Eager gate-by-gate simulator, differentiable through autograd (complex64)."""
+def qsim_torch(x: torch.Tensor, w: torch.Tensor, return_probs: bool = False) -> torch.Tensor:
+    """Eager gate-by-gate simulator, differentiable through autograd (complex64).  ``return_probs``: the
+    (B, 2^n) outcome probabilities instead of <Z_i>."""
     B, n = x.shape
     L = w.shape[0]
     D = 1 << n
@@ -228,6 +233,8 @@ def qsim_torch(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
             state = torch.stack([t0, t1], dim=2).reshape(B, D)
         state = state[:, perm]
     probs = state.real ** 2 + state.imag ** 2
+    if return_probs:
+        return probs
     return probs @ z_signs(n, x.device)
 
 
@@ -236,19 +243,225 @@ def default_backend(device: torch.device) -> str:
     return "hip" if device.type == "cuda" else "cpu"
 
 
-def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None) -> torch.Tensor:
-    """<Z_i> of the QSC circuit for inputs x (B, n) and weights w (L, n, 2).
-
-    ``w`` may also be grouped, (G, L, n, 2) with B % G == 0: sample b then uses
-    w[b // (B/G)] (independent QuantumNAT noise per data stream)."""
+def _check_shapes(x: torch.Tensor, w: torch.Tensor) -> None:
     if x.dim() != 2 or w.dim() not in (3, 4) or w.shape[-2] != x.shape[1] or w.shape[-1] != 2:
         raise ValueError(f"bad shapes x={tuple(x.shape)} w={tuple(w.shape)}")
     if w.dim() == 4 and x.shape[0] % w.shape[0]:
         raise ValueError("batch must be a multiple of the weight-group count")
-    n = x.shape[1]
-    if n < 2:
+    if x.shape[1] < 2:
         raise ValueError("the CNOT ring needs n_qubits >= 2")
+
+
+# ----------------------------------------------------------------------------- finite shots
+HIP_SHOTS_MAX_QUBITS = 12   # csrc/hip/qsim_shots.hip: state, ring gather buffer and CDF in one workgroup's LDS
+MAX_SHOTS = 1 << 20
+_u64 = ctypes.c_uint64
+_M64 = (1 << 64) - 1
+
+
+def _check_shots(shots: int) -> int:
+    shots = int(shots)
+    if not 1 <= shots <= MAX_SHOTS:
+        raise ValueError(f"shots must be in 1..{MAX_SHOTS}, got {shots}")
+    return shots
+
+
+def _split_counter(counter, device):
+    """(host counter, device counter pointer or None): an int is the host part; a CUDA int64 / uint64 scalar
+    tensor is read by the kernel (graph replays see its current value; follow the call with counter_add)."""
+    if isinstance(counter, torch.Tensor):
+        if counter.device.type != "cuda" or counter.numel() != 1 or counter.dtype not in (torch.int64, torch.uint64):
+            raise ValueError("a tensor counter must be a CUDA int64 / uint64 scalar")
+        if device.type != "cuda":
+            raise ValueError("a device counter needs the hip backend")
+        return 0, nat.ptr(counter)
+    return int(counter) & _M64, None
+
+
+def counter_add(counter: torch.Tensor, delta: int = 1) -> None:
+    """``counter += delta`` on the current stream (a one-thread kernel, graph-capturable): launch it after a
+    sampling call that reads ``counter``, so that every replay of a captured graph draws fresh shots."""
+    _split_counter(counter, counter.device)
+    f = nat.fn(nat.hip_lib(), "qd_counter_add", [_p, _u64, _p])
+    nat.check(f(nat.ptr(counter), int(delta) & _M64, nat.stream_ptr(counter.device)), "qd_counter_add")
+
+
+def hip_qsim_probs(x: torch.Tensor, w: torch.Tensor, probs: torch.Tensor, wgroup: int = 0) -> None:
+    """Raw launcher: probs (B, 2^n) fp32 = |amp_k|^2 in natural basis order; n <= 12."""
+    B, n = x.shape
+    f = nat.fn(nat.hip_lib(), "qd_qsim_probs", [_p, _p, _p, _i, _i, _i, _i, _p])
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(probs), B, n, w.shape[-3], wgroup, nat.stream_ptr(x.device)),
+              "qd_qsim_probs")
+
+
+def hip_sample_z(probs: torch.Tensor, E: torch.Tensor, counts: Optional[torch.Tensor], n: int, shots: int,
+                 seed: int = 0, ctr0: int = 0, counter_ptr=None) -> None:
+    """Raw launcher: E (B, n) fp32 / counts (B, n) int32 (nullable) from `shots` draws of every row of probs."""
+    f = nat.fn(nat.hip_lib(), "qd_sample_z", [_p, _p, _p, _i, _i, _i, _u64, _u64, _p, _p])
+    nat.check(f(nat.ptr(probs), nat.ptr(E), nat.ptr(counts) if counts is not None else None, probs.shape[0], n, shots,
+                seed & _M64, ctr0 & _M64, counter_ptr, nat.stream_ptr(probs.device)), "qd_sample_z")
+
+
+def hip_qsim_shots_fwd(x: torch.Tensor, w: torch.Tensor, E: torch.Tensor, counts: Optional[torch.Tensor], shots: int,
+                       seed: int = 0, ctr0: int = 0, counter_ptr=None, wgroup: int = 0) -> None:
+    """Raw launcher of the fused kernel: state -> probabilities -> shots in one launch; n <= 12."""
+    B, n = x.shape
+    f = nat.fn(nat.hip_lib(), "qd_qsim_shots_fwd", [_p, _p, _p, _p, _i, _i, _i, _i, _i, _u64, _u64, _p, _p])
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(E), nat.ptr(counts) if counts is not None else None, B, n,
+                w.shape[-3], wgroup, shots, seed & _M64, ctr0 & _M64, counter_ptr, nat.stream_ptr(x.device)),
+              "qd_qsim_shots_fwd")
+
+
+def _hip_shots_limit(n: int) -> None:
+    if n > HIP_SHOTS_MAX_QUBITS:
+        raise NotImplementedError(f"the HIP finite-shot kernels support n <= {HIP_SHOTS_MAX_QUBITS} qubits, got {n}")
+
+
+@torch.no_grad()
+def qsim_probs(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None) -> torch.Tensor:
+    """Outcome probabilities |amp_k|^2 of the QSC circuit, (B, 2^n) in natural basis order (the ``qml.probs``
+    counterpart): fp32 on ``hip`` (n <= 12), fp64 on ``cpu``, the eager simulator's on ``torch``.  No autograd."""
+    _check_shapes(x, w)
+    B, n = x.shape
     be = backend if backend not in (None, "auto") else default_backend(x.device)
+    if be == "hip":
+        if x.device.type != "cuda":
+            raise RuntimeError("hip backend needs CUDA/HIP tensors")
+        _hip_shots_limit(n)
+        x = x.detach().float().contiguous()
+        w = w.detach().float().contiguous()
+        probs = torch.empty(B, 1 << n, device=x.device, dtype=torch.float32)
+        if B > 0:
+            hip_qsim_probs(x, w, probs, wgroup_of(x, w))
+        return probs
+    if w.dim() == 4:  # host backends: run per group
+        return torch.cat([qsim_probs(xc, w[g], be) for g, xc in enumerate(x.chunk(w.shape[0]))], dim=0)
+    if be == "cpu":
+        if x.device.type != "cpu":
+            raise RuntimeError("cpu backend needs CPU tensors")
+        x = x.detach().float().contiguous()
+        w = w.detach().float().contiguous()
+        probs = torch.empty(B, 1 << n, dtype=torch.float64)
+        f = nat.fn(nat.cpu_lib(), "qd_cpu_qsim_probs", [_p, _p, _p, _i, _i, _i])
+        nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(probs), B, n, w.shape[0]), "qd_cpu_qsim_probs")
+        return probs
+    if be == "torch":
+        return qsim_torch(x, w, return_probs=True)
+    raise ValueError(f"unknown backend {be!r}")
+
+
+@torch.no_grad()
+def sample_z(probs: torch.Tensor, shots: int, seed: int = 0, counter=0, return_counts: bool = False):
+    """Finite-shot <Z_i> from outcome probabilities (B, 2^n), a normalised distribution per row (cast to fp32):
+    E (B, n) fp32, and with ``return_counts`` also counts (B, n) int32, the shots that read 1 on wire i.
+
+    Dispatches on the tensor's device: csrc/hip/qsim_shots.hip on the GPU, the sequential C++ sampler on the
+    host -- the same integer contract (Philox4x32-10 keyed by ``seed``, counter (shot / 4, row, counter)), so the
+    two agree bit for bit on the same fp32 probabilities.  2 <= n <= 12."""
+    shots = _check_shots(shots)
+    if probs.dim() != 2 or probs.shape[1] < 4 or probs.shape[1] & (probs.shape[1] - 1):
+        raise ValueError(f"probs must be (B, 2^n) with n >= 2, got {tuple(probs.shape)}")
+    B, n = probs.shape[0], probs.shape[1].bit_length() - 1
+    if n > HIP_SHOTS_MAX_QUBITS:   # (the host sampler keeps the kernels' range: one contract)
+        raise NotImplementedError(f"the shot samplers support n <= {HIP_SHOTS_MAX_QUBITS} qubits, got {n}")
+    probs = probs.detach().float().contiguous()
+    ctr0, cptr = _split_counter(counter, probs.device)
+    E = torch.empty(B, n, device=probs.device, dtype=torch.float32)
+    counts = torch.empty(B, n, device=probs.device, dtype=torch.int32)
+    if B > 0 and probs.device.type == "cuda":
+        hip_sample_z(probs, E, counts, n, shots, int(seed), ctr0, cptr)
+    elif B > 0:
+        f = nat.fn(nat.cpu_lib(), "qd_cpu_sample_z", [_p, _p, _p, _i, _i, _i, _u64, _u64])
+        nat.check(f(nat.ptr(probs), nat.ptr(E), nat.ptr(counts), B, n, shots, int(seed) & _M64, ctr0),
+                  "qd_cpu_sample_z")
+    return (E, counts) if return_counts else E
+
+
+class _QSimShotsHIP(torch.autograd.Function):
+    """Forward: the fused finite-shot kernel.  Backward: the exact adjoint (shot noise is straight-through)."""
+
+    @staticmethod
+    def forward(ctx, x, w, wgroup, shots, seed, ctr0, cptr):
+        B, n = x.shape
+        x = x.detach().float().contiguous()
+        w = w.detach().float().contiguous()
+        E = torch.empty(B, n, device=x.device, dtype=torch.float32)
+        if B > 0:
+            hip_qsim_shots_fwd(x, w, E, None, shots, seed, ctr0, cptr, wgroup)
+        ctx.save_for_backward(x, w)
+        return E
+
+    @staticmethod
+    def backward(ctx, gE):
+        dx, dw, _ = _QSimHIP.backward(ctx, gE)
+        return dx, dw, None, None, None, None, None
+
+
+class _QSimShotsCPU(torch.autograd.Function):
+    """Forward: simulate (fp64), then sample.  Backward: the exact adjoint (shot noise is straight-through)."""
+
+    @staticmethod
+    def forward(ctx, x, w, shots, seed, ctr0):
+        x = x.detach().float().contiguous()
+        w = w.detach().float().contiguous()
+        ctx.save_for_backward(x, w)
+        return sample_z(qsim_probs(x, w, "cpu"), shots, seed, ctr0)
+
+    @staticmethod
+    def backward(ctx, gE):
+        dx, dw = _QSimCPU.backward(ctx, gE)
+        return dx, dw, None, None, None
+
+
+class _ReplaceValue(torch.autograd.Function):
+    """value, with the gradient handed to `exact` unchanged (straight-through)."""
+
+    @staticmethod
+    def forward(ctx, exact, value):
+        return value.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots: Optional[int] = None, seed: int = 0,
+         counter=0) -> torch.Tensor:
+    """<Z_i> of the QSC circuit for inputs x (B, n) and weights w (L, n, 2).
+
+    ``w`` may also be grouped, (G, L, n, 2) with B % G == 0: sample b then uses
+    w[b // (B/G)] (independent QuantumNAT noise per data stream).
+
+    ``shots`` (None / 0: the exact expectation): every <Z_i> is estimated from that many measurement shots of
+    the final state -- the fused kernel of csrc/hip/qsim_shots.hip on ``hip`` (n <= 12), simulate-then-sample
+    on ``cpu``; ``torch`` has no sampler.  The shots of a call are a function of (``seed``, ``counter``, row);
+    ``counter`` is an int, or on ``hip`` a CUDA int64 / uint64 scalar tensor the kernel reads (advance it with
+    ``counter_add`` after the call: graph replays then draw fresh shots).  The BACKWARD is the exact adjoint of
+    the same (x, w): shot noise is straight-through, the way QuantumNAT's weight noise is treated."""
+    _check_shapes(x, w)
+    n = x.shape[1]
+    be = backend if backend not in (None, "auto") else default_backend(x.device)
+    if shots:
+        shots = _check_shots(shots)
+        if be == "torch":
+            raise ValueError("the torch backend has no finite-shot sampler; use hip or cpu")
+        if be == "hip":
+            if x.device.type != "cuda":
+                raise RuntimeError("hip backend needs CUDA/HIP tensors")
+            _hip_shots_limit(n)
+            if 2 * n * w.shape[-3] > 256 and n > HIP_REG_MAX_QUBITS:   # (the adjoint's limit, as for the exact call)
+                raise NotImplementedError("large-n HIP simulator supports 2*n*L <= 256")
+            ctr0, cptr = _split_counter(counter, x.device)
+            return _QSimShotsHIP.apply(x, w, wgroup_of(x, w), shots, int(seed), ctr0, cptr)
+        if be == "cpu":
+            if x.device.type != "cpu":
+                raise RuntimeError("cpu backend needs CPU tensors")
+            ctr0, _ = _split_counter(counter, x.device)
+            if w.dim() == 4:  # exact per-group forward for the graph, its values replaced by the sampled ones
+                E = sample_z(qsim_probs(x, w, "cpu"), shots, int(seed), ctr0)
+                return _ReplaceValue.apply(qsim(x, w, "cpu"), E)
+            return _QSimShotsCPU.apply(x, w, shots, int(seed), ctr0)
+        raise ValueError(f"unknown backend {be!r}")
     if be == "hip":
         if x.device.type != "cuda":
             raise RuntimeError("hip backend needs CUDA/HIP tensors")

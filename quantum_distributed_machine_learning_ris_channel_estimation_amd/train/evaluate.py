@@ -157,10 +157,22 @@ class model_val:
             if clf is None:
                 out[f"nmse_{tag}"], out[f"acc_{tag}"] = float("nan"), float("nan")
                 continue
+            # qsc_shots > 0: the quantum SC's circuit is measured with that many shots per sample (seeded by cfg.seed)
+            shots = int(self.qsc_shots) if tag == "quantum" and getattr(clf, "use_quantum", False) else 0
             if eng is not None and (eng.sc if tag == "classical" else eng.qsc) is not None:
-                pred = eng.classify(x, tag)   # the HIP kernels: classifier, experts, routed FC (train/infer.py)
+                # the HIP kernels: classifier, experts, routed FC (train/infer.py)
+                pred = eng.classify(x, tag, shots=shots, seed=self.seed) if shots else eng.classify(x, tag)
             else:   # (CPU, or the classical-fallback QSC ablation: torch)
-                pred = torch.cat([clf(x[i:i + chunk]).argmax(1) for i in range(0, x.shape[0], chunk)])
+                if shots:
+                    ql = clf.qlayer
+                    exact = (ql.shots, ql.shot_seed, ql._shot_calls)
+                    ql.shots = shots
+                    ql.manual_shot_seed(self.seed)
+                try:
+                    pred = torch.cat([clf(x[i:i + chunk]).argmax(1) for i in range(0, x.shape[0], chunk)])
+                finally:
+                    if shots:
+                        ql.shots, ql.shot_seed, ql._shot_calls = exact
             saved = None
             if self.bn_adapt:   # (GPU: the HIP training conv forward computes the statistics, no MIOpen)
                 saved = eng.recalibrate_bn(convs, x, pred) if eng is not None else recalibrate_bn(convs, x, pred)
@@ -238,6 +250,7 @@ class model_val:
             "NMSE_HDCE_Quantum_dB": db(nmse_quantum),
             "Accuracy_Classical": list(map(float, acc_classical)),
             "Accuracy_Quantum": list(map(float, acc_quantum)),
+            "qsc_shots": int(self.qsc_shots),   # (0: exact expectation values)
         }
         if nmse_lmmse is not None:
             results["NMSE_LMMSE_dB"] = db(nmse_lmmse)
