@@ -245,6 +245,33 @@ __device__ void bn_bwd_build(const BnBwd& bn, const float* __restrict__ st, floa
   }
 }
 
+// Layer 1 reading the pilots straight from the HBM-resident store (gather.hip's batch assembly without its launch:
+// the x1 copy is never made).  Forward (GatherSrc): sample n = u * B + b of expert e is the plane of stream
+// s = e * U + u, store row perm[c + b], c = the step's batch cursor under gather_step_kernel's guard; the workgroup
+// also writes rowoff / rowden of the samples it owns -- gather_step_kernel's expressions.  The cursor is only read
+// (the step's optimizer launch advances it).  Weight gradient (RowSrc): the same planes through the rowoff the
+// forward wrote, so the cursor is not consulted a second time.
+struct GatherSrc {
+  const long* perm;          // null: the input is the gathered x1
+  const int* cursor;
+  long nperm;
+  const float* Yp;
+  long yp_stream_stride;     // floats per stream of the store
+  long lab_stream_rows;      // label rows per stream (rowoff's row space)
+  const float* rowpow_l;     // per-row label / perfect-channel powers (rowpow_p nullable)
+  const float* rowpow_p;
+  int* rowoff;               // (U * B * E) out
+  float2* rowden;            // (U * B * E) out
+  const float2* scale;       // nullable (strong scaling): per-stream factors of rowden
+  int plane, off, adv;       // 2 * H * W; this rank's offset into the global batch; the cursor's advance
+};
+struct RowSrc {
+  const int* rowoff;         // null: the input is the gathered x1
+  const float* Yp;
+  long yp_stream_stride, lab_stream_rows;
+  int plane;
+};
+
 // ------------------------------------------------------------------------------------------
 // conv3x3_kernel: forward (and data-gradient) implicit GEMM
 // grid: (U * chunks, E); block 256 (4 waves); each wave owns `spw` consecutive samples.
@@ -257,7 +284,8 @@ __device__ __forceinline__ void conv3x3_body(const TIN* __restrict__ xin, const 
                                              const float* __restrict__ st_in, const uint16_t* __restrict__ wt,
                                              void* __restrict__ out, float* __restrict__ stats, int E, int B,
                                              int chunks, int spw, BnFwd bnf, BnBwd bnb, BnRed brd,
-                                             unsigned long long* __restrict__ stamps, int bx, int by, int gdx) {
+                                             unsigned long long* __restrict__ stamps, int bx, int by, int gdx,
+                                             GatherSrc gs = GatherSrc{}) {
   // STAMP (diagnostic builds): per wave [0] start [1] weights + BN params staged [2] first sample
   // staged [3] first sample's MFMAs + epilogue [4] all samples [5] end
   unsigned long long ts[8] = {};
@@ -314,13 +342,41 @@ __device__ __forceinline__ void conv3x3_body(const TIN* __restrict__ xin, const 
   [[maybe_unused]] uint4 rv[RAWIN ? 1 : GR][2][QV];
   [[maybe_unused]] uint4 rz[INM == IN_BNBWD ? GR : 1][2];
   [[maybe_unused]] float rr[RAWIN ? GR : 1];
+  // (GatherSrc) lane k holds the store row of this wave's k-th sample; its rowoff / rowden go out here
+  [[maybe_unused]] int grow = 0;
+  [[maybe_unused]] const TIN* gsrc = xin;
+  if constexpr (RAWIN) {
+    if (gs.perm != nullptr) {
+      int c = *gs.cursor;
+      if (c < 0 || c + gs.adv > gs.nperm) c = 0;   // (gather_step_kernel's guard)
+      c += gs.off;
+      const int U = gdx / chunks, s = e * U + u;
+      if (n0 + lane < nend) {
+        const long row = gs.perm[c + (n0 - u * B) + lane];
+        grow = (int)row;
+        const size_t r = (size_t)(n0 + lane) * E + e;
+        const long ro = s * gs.lab_stream_rows + row;
+        gs.rowoff[r] = (int)ro;
+        float2 d = make_float2(gs.rowpow_l[ro], gs.rowpow_p ? gs.rowpow_p[ro] : 0.f);
+        if (gs.scale) {
+          const float2 f = gs.scale[s];
+          d.x *= f.x;
+          d.y *= f.y;
+        }
+        gs.rowden[r] = d;
+      }
+      gsrc = reinterpret_cast<const TIN*>(gs.Yp) + (size_t)s * gs.yp_stream_stride;
+    }
+  }
   auto load_group = [&](int n, int g0) {
-    const size_t base = ((size_t)n * E + e) * CIN * G::HW;
+    size_t base = ((size_t)n * E + e) * CIN * G::HW;
+    if constexpr (RAWIN)
+      if (gs.perm != nullptr) base = (size_t)__shfl(grow, n - n0) * gs.plane;
 #pragma unroll
     for (int k = 0; k < GR; ++k) {
       const int it = g0 + k;
       if constexpr (RAWIN) {
-        rr[k] = ldf<TIN>(xin, base + lane + 64 * it);
+        rr[k] = ldf<TIN>(gsrc, base + lane + 64 * it);
       } else {
         // item i: channel pair i % NPAIR, positions [8 (i / NPAIR), +8)
         const int i = lane + 64 * it, pr = i % NPAIR, sg = i / NPAIR;
@@ -614,6 +670,16 @@ __global__ void __launch_bounds__(256, 2) conv3x3_kernel(const TIN* __restrict__
                                                       unsigned long long* __restrict__ stamps = nullptr) {
   conv3x3_body<CIN, H, W, INM, OUTM, DGRAD, TIN, STAMP>(xin, zaux, st_in, wt, out, stats, E, B, chunks, spw, bnf, bnb,
                                                         brd, stamps, blockIdx.x, blockIdx.y, gridDim.x);
+}
+
+// layer 1's training forward with the batch gather inside (GatherSrc): conv3x3_kernel<2, ..., IN_RAW_F32, ...>'s body
+template <int W>
+__global__ void __launch_bounds__(256, 2) conv3x3_l1_gather_kernel(const uint16_t* __restrict__ wt,
+                                                                void* __restrict__ out, float* __restrict__ stats,
+                                                                int E, int B, int chunks, int spw, GatherSrc gs) {
+  conv3x3_body<2, 16, W, IN_RAW_F32, OUT_Z_STATS, false, float>(nullptr, nullptr, nullptr, wt, out, stats, E, B, chunks,
+                                                                spw, BnFwd{}, BnBwd{}, BnRed{}, nullptr, blockIdx.x,
+                                                                blockIdx.y, gridDim.x, gs);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1491,6 +1557,42 @@ __global__ void pack_weights_multi_kernel(PackJobs jobs) {
   pack_weights_body(jobs.w[j], jobs.out[j], jobs.cin[j], jobs.ks[j], jobs.dgrad[j], s, blockIdx.y);
 }
 
+// Several independent deterministic slab row sums as one argument (slab_rows_sum4_multi_kernel below, blockIdx.z =
+// job): conv weight slabs, BN and FC-bias partials, the quantum-layer and QSC preprocess slabs.  Jobs whose width is
+// not a multiple of 4 (or whose buffers are not 16-byte aligned) take a scalar path.
+constexpr int kSlabJobs = 16;
+struct SlabJobs {
+  const float* slab[kSlabJobs];
+  float* out[kSlabJobs];
+  int groups[kSlabJobs], rows[kSlabJobs], width[kSlabJobs], ld[kSlabJobs], vec[kSlabJobs];
+  int accumulate;
+};
+
+// Slab jobs HOSTED by a backward launch that is on the chain anyway (layer 1's weight gradient, a fused layer
+// backward): whole extra grid rows of workgroups, each one (job, group, 64 columns) of slab_rows_sum4_multi_kernel's
+// grid, run that kernel's bodies on slabs that EARLIER launches completed -- nothing of the hosting launch's own
+// output is read, so no workgroup waits for another.  Same rows per thread, same order, same combine: the sums are
+// those of qd_slab_rows_sum_multi, bit for bit.
+struct HostedSlabs {
+  SlabJobs jobs;
+  int wg0[kSlabJobs + 1];   // first workgroup of each job (prefix sums of groups x ceil(width / 64)); wg0[n] = all
+  int n;                    // jobs (0: none hosted)
+  int rows_y;               // grid rows of gridDim.x workgroups that serve them
+  int first;                // the slab rows come first in block order (blockIdx.y < rows_y); else after the host's
+};
+__device__ void hosted_slab_wg(const HostedSlabs& hs, int w, float* lds);
+// true: this workgroup served a slab job (it is done); else `by` is the hosting kernel's own row index
+__device__ __forceinline__ bool hosted_slabs_take(const HostedSlabs& hs, float* lds, int& by) {
+  if (hs.n == 0) return false;
+  const int sy = hs.first ? by : by - ((int)gridDim.y - hs.rows_y);
+  if (sy >= 0 && sy < hs.rows_y) {
+    hosted_slab_wg(hs, sy * (int)gridDim.x + (int)blockIdx.x, lds);
+    return true;
+  }
+  if (hs.first) by -= hs.rows_y;
+  return false;
+}
+
 // ------------------------------------------------------------------------------------------
 // conv3x3_wgrad: dW[e][co][ci][tap] partials.  grid (U*chunks, E), block 256, `spb` samples
 // per workgroup; slab[(e * U*chunks + blockIdx.x)][co][ci][tap].
@@ -1500,7 +1602,8 @@ template <int CIN, int H, int W, int INM, typename TIN, typename TDH>
 __device__ __forceinline__ void conv3x3_wgrad_body(const TIN* __restrict__ xin, const float* __restrict__ st_prev,
                                                    const TDH* __restrict__ dh, const uint16_t* __restrict__ z,
                                                    const float* __restrict__ st, float* __restrict__ slab, int E, int B,
-                                                   int chunks, int spb, BnBwd bnb, int bx, int by, int gdx) {
+                                                   int chunks, int spb, BnBwd bnb, int bx, int by, int gdx,
+                                                   RowSrc rs = RowSrc{}) {
   using G = Geo<H, W>;
   constexpr int MTW = (9 * CIN + 31) / 32;        // accumulator tiles (9 for CIN=32, 1 for CIN=2)
   constexpr int XCS = G::HP * W + 8;              // channel stride of the shifted copies (bf16)
@@ -1530,13 +1633,32 @@ __device__ __forceinline__ void conv3x3_wgrad_body(const TIN* __restrict__ xin, 
 
   // ---- one-sample-ahead register prefetch: sample n+1's loads fly during sample n's MFMAs ----
   uint4 xr[XIT][XQ], dr[DIT][DQ], zr[DIT];
+  // (RowSrc, layer 1) sample n's pilots sit in the store at the row the forward wrote into rowoff; the row of the
+  // NEXT prefetch is loaded one sample ahead (rnext), so only the first sample waits for its row
+  [[maybe_unused]] const TIN* xsrc = xin;
+  [[maybe_unused]] long rsub = 0;
+  [[maybe_unused]] int rnext = 0;
+  if constexpr (INM == IN_RAW_F32) {
+    if (rs.rowoff != nullptr) {
+      const int U = gdx / chunks, s = e * U + u;
+      xsrc = reinterpret_cast<const TIN*>(rs.Yp) + (size_t)s * rs.yp_stream_stride;
+      rsub = s * rs.lab_stream_rows;
+      if (n0 < nend) rnext = rs.rowoff[(size_t)n0 * E + e];
+    }
+  }
   auto prefetch = [&](int n) {
-    const size_t xb = ((size_t)n * E + e) * CIN * G::HW;
+    size_t xb = ((size_t)n * E + e) * CIN * G::HW;
+    if constexpr (INM == IN_RAW_F32) {
+      if (rs.rowoff != nullptr) {
+        xb = (size_t)(rnext - rsub) * rs.plane;
+        rnext = rs.rowoff[(size_t)(n + 1 < nend ? n + 1 : n) * E + e];
+      }
+    }
 #pragma unroll
     for (int k = 0; k < XIT; ++k) {
       const int i = tid + 256 * k;
       if (XN % 256 == 0 || i < XN) {
-        const uint4* src = reinterpret_cast<const uint4*>(xin + xb + (size_t)(i / H) * G::HW + (i % H) * W);
+        const uint4* src = reinterpret_cast<const uint4*>(xsrc + xb + (size_t)(i / H) * G::HW + (i % H) * W);
 #pragma unroll
         for (int q = 0; q < XQ; ++q) xr[k][q] = src[q];
       }
@@ -1675,9 +1797,13 @@ __global__ void __launch_bounds__(256, 2) conv3x3_wgrad_kernel(const TIN* __rest
                                                             const TDH* __restrict__ dh,
                                                             const uint16_t* __restrict__ z,
                                                             const float* __restrict__ st, float* __restrict__ slab,
-                                                            int E, int B, int chunks, int spb, BnBwd bnb) {
-  conv3x3_wgrad_body<CIN, H, W, INM, TIN, TDH>(xin, st_prev, dh, z, st, slab, E, B, chunks, spb, bnb, blockIdx.x,
-                                               blockIdx.y, gridDim.x);
+                                                            int E, int B, int chunks, int spb, BnBwd bnb,
+                                                            HostedSlabs hs, RowSrc rs) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int by = blockIdx.y;
+  if (hosted_slabs_take(hs, reinterpret_cast<float*>(smem), by)) return;   // (extra grid rows: hosted slab sums)
+  conv3x3_wgrad_body<CIN, H, W, INM, TIN, TDH>(xin, st_prev, dh, z, st, slab, E, B, chunks, spb, bnb, blockIdx.x, by,
+                                               gridDim.x, rs);
 }
 
 // One launch for a 32-channel layer's weight gradient AND data gradient (bf16 dh / dx): the two are
@@ -1743,8 +1869,12 @@ __global__ void __launch_bounds__(256, W == 8 ? 2 : 1) conv3x3_bwd_kernel(const 
                                                           const uint16_t* __restrict__ z, const float* __restrict__ st,
                                                           float* __restrict__ slab, const uint16_t* __restrict__ wt,
                                                           uint16_t* __restrict__ dx, float* __restrict__ part, int E,
-                                                          int B, int chunks, int spb, BnBwd bnb, LossFinish lf) {
-  if ((int)blockIdx.y == E) {   // the extra row (lf.part set): block 0 hosts the HDCE loss finish (when layer 3's
+                                                          int B, int chunks, int spb, BnBwd bnb, LossFinish lf,
+                                                          HostedSlabs hs) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int by = blockIdx.y;
+  if (hosted_slabs_take(hs, reinterpret_cast<float*>(smem), by)) return;   // (extra grid rows: hosted slab sums)
+  if (by == E) {   // the extra row (lf.part set): block 0 hosts the HDCE loss finish (when layer 3's
     if (blockIdx.x == 0) loss_finish_body(lf);   // BN reduction rode in the FC data gradient, the launch that
     return;                                      // hosted it is gone)
   }
@@ -1758,7 +1888,6 @@ __global__ void __launch_bounds__(256, W == 8 ? 2 : 1) conv3x3_bwd_kernel(const 
   constexpr int XQ = W / 8;                    // 16-byte vectors per image row
   constexpr bool PREF = HW <= 128;             // one-sample-ahead register prefetch (P128)
   static_assert(2 * KSA + KSA / 4 == 18 * TPW, "wgrad steps pair with dgrad k-steps");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
   __bf16* X = reinterpret_cast<__bf16*>(smem);       // [kw][ci][row][w]
   __bf16* DZ = X + BG::X_EL;                         // [co][p]
   __bf16* T = DZ + BG::DZ_EL;                        // [pixel][32] swizzled
@@ -1768,7 +1897,7 @@ __global__ void __launch_bounds__(256, W == 8 ? 2 : 1) conv3x3_bwd_kernel(const 
   float* prp = prm + CO * NST;                               // previous layer's records (x, reduction)
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int hh = lane >> 5, l32 = lane & 31;
-  const int bx = blockIdx.x, e = blockIdx.y, u = bx / chunks, chunk = bx % chunks;
+  const int bx = blockIdx.x, e = by, u = bx / chunks, chunk = bx % chunks;
   const int EC = E * CO;
   const int n0 = u * B + chunk * spb, nend = min((u + 1) * B, n0 + spb);
 
@@ -2667,19 +2796,12 @@ __global__ void __launch_bounds__(256) slab_rows_sum4_kernel(const float* __rest
   slab_rows_sum4_body(slab, out, rows, width, width, blockIdx.y, blockIdx.x, accumulate);
 }
 
-// Several independent slab sums in one launch (blockIdx.z = job): every gradient-slab reduction of
-// a step phase (conv weight slabs, quantum-layer slab, QSC preprocess slab) at once.  Jobs whose
-// width is not a multiple of 4 (or whose buffers are not 16-byte aligned) take a scalar path.
-constexpr int kSlabJobs = 16;
-struct SlabJobs {
-  const float* slab[kSlabJobs];
-  float* out[kSlabJobs];
-  int groups[kSlabJobs], rows[kSlabJobs], width[kSlabJobs], ld[kSlabJobs], vec[kSlabJobs];
-  int accumulate;
-};
-__device__ __forceinline__ void slab_rows_sum1_body(const float* __restrict__ slab, float* __restrict__ out, int rows,
-                                                    int width, int ld, int g, int bx, int accumulate) {
-  __shared__ float red1[16][64];
+// Several independent slab sums in one launch (blockIdx.z = job, SlabJobs above): every gradient-slab reduction of
+// a step phase (conv weight slabs, quantum-layer slab, QSC preprocess slab) at once.
+// (the *_core forms take their 4 KB LDS scratch from the caller: a hosting kernel lends its dynamic LDS)
+__device__ __forceinline__ void slab_rows_sum1_core(const float* __restrict__ slab, float* __restrict__ out, int rows,
+                                                    int width, int ld, int g, int bx, int accumulate,
+                                                    float (*red1)[64]) {
   const int tq = threadIdx.x & 15, ty = threadIdx.x >> 4;
   float t[4] = {0.f, 0.f, 0.f, 0.f};
   const float* s = slab + (size_t)g * rows * ld;
@@ -2701,6 +2823,11 @@ __device__ __forceinline__ void slab_rows_sum1_body(const float* __restrict__ sl
     if (i < width) out[(size_t)g * width + i] = (accumulate ? out[(size_t)g * width + i] : 0.f) + acc;
   }
 }
+__device__ __forceinline__ void slab_rows_sum1_body(const float* __restrict__ slab, float* __restrict__ out, int rows,
+                                                    int width, int ld, int g, int bx, int accumulate) {
+  __shared__ float red1[16][64];
+  slab_rows_sum1_core(slab, out, rows, width, ld, g, bx, accumulate, red1);
+}
 __global__ void __launch_bounds__(256) slab_rows_sum4_multi_kernel(SlabJobs jobs) {
   const int j = blockIdx.z;
   if (blockIdx.y >= jobs.groups[j] || blockIdx.x * 64 >= jobs.width[j]) return;
@@ -2712,10 +2839,10 @@ __global__ void __launch_bounds__(256) slab_rows_sum4_multi_kernel(SlabJobs jobs
                         jobs.accumulate);
 }
 
-template <int SR>
-__device__ __forceinline__ void slab_rows_sum4_body(const float* __restrict__ slab, float* __restrict__ out, int rows,
-                                                    int width, int ld, int g, int bx, int accumulate) {
-  __shared__ float4 red[16][16];
+template <int SR = 8>
+__device__ __forceinline__ void slab_rows_sum4_core(const float* __restrict__ slab, float* __restrict__ out, int rows,
+                                                    int width, int ld, int g, int bx, int accumulate,
+                                                    float4 (*red)[16]) {
   const int tq = threadIdx.x & 15, ty = threadIdx.x >> 4;
   const int i = (bx * 16 + tq) * 4;
   float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -2759,6 +2886,28 @@ __device__ __forceinline__ void slab_rows_sum4_body(const float* __restrict__ sl
     cur.w += acc.w;
     *o = cur;
   }
+}
+template <int SR>
+__device__ __forceinline__ void slab_rows_sum4_body(const float* __restrict__ slab, float* __restrict__ out, int rows,
+                                                    int width, int ld, int g, int bx, int accumulate) {
+  __shared__ float4 red[16][16];
+  slab_rows_sum4_core<SR>(slab, out, rows, width, ld, g, bx, accumulate, red);
+}
+
+// workgroup w of a hosting launch's slab rows: (job k, group, 64 columns) as slab_rows_sum4_multi_kernel's grid
+// would have run it; lds: 4 KB of the hosting kernel's (16-byte aligned) dynamic LDS
+__device__ void hosted_slab_wg(const HostedSlabs& hs, int w, float* lds) {
+  if (w >= hs.wg0[hs.n]) return;   // (the last row's spare workgroups)
+  int k = 0;
+  while (k + 1 < hs.n && w >= hs.wg0[k + 1]) ++k;
+  const SlabJobs& jb = hs.jobs;
+  const int cpg = (jb.width[k] + 63) / 64, lb = w - hs.wg0[k], g = lb / cpg, bx = lb % cpg;
+  if (jb.vec[k])
+    slab_rows_sum4_core(jb.slab[k], jb.out[k], jb.rows[k], jb.width[k], jb.ld[k], g, bx, jb.accumulate,
+                        reinterpret_cast<float4(*)[16]>(lds));
+  else
+    slab_rows_sum1_core(jb.slab[k], jb.out[k], jb.rows[k], jb.width[k], jb.ld[k], g, bx, jb.accumulate,
+                        reinterpret_cast<float(*)[64]>(lds));
 }
 
 }  // namespace conv
@@ -2835,6 +2984,21 @@ QD_API int qd_conv_fwd(int layer, const void* xin, const float* st_prev, const u
                                     dim3(256), fwd_smem(32, H, W), s, (const uint16_t*)xin, nullptr, st_prev, w, z,
                                     stats, E, B, chunks, spw, bf, bb, BnRed{}))
   }
+  return (int)hipGetLastError();
+}
+
+// layer 1's qd_conv_fwd with the step's batch gather inside (conv3x3_l1_gather_kernel): z / stats as qd_conv_fwd's
+// on the x1 that qd_gather_cursor would have written, plus its rowoff / rowden.  The cursor is read, never advanced.
+QD_API int qd_conv_fwd_gather(const GatherSrc* src, const uint16_t* w, uint16_t* z, float* stats, int N, int E, int B,
+                              int H, int W, int chunks, int spw, void* stream) {
+  if (!src || B < 1 || N % B || chunks * 4 * spw < B || spw < 1 || spw > 64) return (int)hipErrorInvalidValue;
+  const GatherSrc g = *src;
+  if (!g.perm || !g.cursor || !g.Yp || !g.rowpow_l || !g.rowoff || !g.rowden || g.plane != 2 * H * W || g.off < 0 ||
+      g.adv < g.off + B || g.nperm < g.adv)
+    return (int)hipErrorInvalidValue;
+  dim3 grid((N / B) * chunks, E);
+  QD_GEOM(WW, hipLaunchKernelGGL((conv3x3_l1_gather_kernel<WW>), grid, dim3(256), fwd_smem(2, H, W),
+                                  (hipStream_t)stream, w, z, stats, E, B, chunks, spw, g))
   return (int)hipGetLastError();
 }
 
@@ -3013,17 +3177,43 @@ static size_t wgrad_smem(int cin, int H, int W) {
 // weight-gradient partials: slab (E, U*chunks, 32*CIN*9).  layer 1: x = raw f32 (CIN=2);
 // layers 2,3: x = BN+ReLU(z_prev) (st_prev).  bnb (nullable): this layer's BN backward coefficients
 // from the reduction partials in-kernel, and dgamma / dbeta written by one workgroup per expert.
-QD_API int qd_conv_wgrad(int layer, const void* xin, const float* st_prev, const void* dh, int dh_bf16,
-                         const uint16_t* z, const float* st, float* slab, int N, int E, int B, int H, int W, int chunks,
-                         int spb, const BnBwd* bnb, void* stream) {
+// hosted (nullable): slab jobs served by extra grid rows of this launch (HostedSlabs; the caller fills jobs.slab /
+// out / groups / rows / width / ld / accumulate, n and first -- the rest is derived here)
+static bool hosted_prepare(const HostedSlabs* in, int gx, HostedSlabs& hs) {
+  hs = HostedSlabs{};
+  if (!in || in->n == 0) return true;
+  if (in->n < 0 || in->n > kSlabJobs || gx < 1) return false;
+  hs = *in;
+  SlabJobs& jb = hs.jobs;
+  hs.wg0[0] = 0;
+  for (int j = 0; j < hs.n; ++j) {
+    if (jb.ld[j] < jb.width[j] || jb.groups[j] < 1 || jb.rows[j] < 1 || jb.width[j] < 1) return false;
+    jb.vec[j] = !(jb.width[j] % 4 || jb.ld[j] % 4 || ((uintptr_t)jb.slab[j] & 15) || ((uintptr_t)jb.out[j] & 15));
+    hs.wg0[j + 1] = hs.wg0[j] + jb.groups[j] * ((jb.width[j] + 63) / 64);
+  }
+  hs.rows_y = (hs.wg0[hs.n] + gx - 1) / gx;
+  hs.first = hs.first != 0;
+  return true;
+}
+
+// rows (nullable, layer 1 only): the pilots read from the store through rowoff (RowSrc) instead of xin
+QD_API int qd_conv_wgrad_slabs(int layer, const void* xin, const float* st_prev, const void* dh, int dh_bf16,
+                               const uint16_t* z, const float* st, float* slab, int N, int E, int B, int H, int W,
+                               int chunks, int spb, const BnBwd* bnb, const HostedSlabs* hosted, const RowSrc* rows,
+                               void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const BnBwd bb = bnb ? *bnb : BnBwd{};
-  dim3 grid((N / B) * chunks, E);
+  const RowSrc rsrc = rows ? *rows : RowSrc{};
+  if (rsrc.rowoff && (layer != 1 || !rsrc.Yp || rsrc.plane != 2 * H * W)) return (int)hipErrorInvalidValue;
+  if (!rsrc.rowoff && !xin) return (int)hipErrorInvalidValue;
+  HostedSlabs hs;
+  if (!hosted_prepare(hosted, (N / B) * chunks, hs)) return (int)hipErrorInvalidValue;
+  dim3 grid((N / B) * chunks, E + hs.rows_y);
   if (chunks * spb < B) return (int)hipErrorInvalidValue;
 #define QD_WG(CIN_, INM_, TIN_, TDH_)                                                                              \
   QD_GEOM(WW, hipLaunchKernelGGL((conv3x3_wgrad_kernel<CIN_, 16, WW, INM_, TIN_, TDH_>), grid, dim3(256),         \
                                   wgrad_smem(CIN_, H, W), s, (const TIN_*)xin, st_prev, (const TDH_*)dh, z, st, slab, \
-                                  E, B, chunks, spb, bb))
+                                  E, B, chunks, spb, bb, hs, rsrc))
   if (layer == 1) {
     if (dh_bf16) { QD_WG(2, IN_RAW_F32, float, uint16_t) } else { QD_WG(2, IN_RAW_F32, float, float) }
   } else {
@@ -3031,6 +3221,12 @@ QD_API int qd_conv_wgrad(int layer, const void* xin, const float* st_prev, const
   }
 #undef QD_WG
   return (int)hipGetLastError();
+}
+QD_API int qd_conv_wgrad(int layer, const void* xin, const float* st_prev, const void* dh, int dh_bf16,
+                         const uint16_t* z, const float* st, float* slab, int N, int E, int B, int H, int W, int chunks,
+                         int spb, const BnBwd* bnb, void* stream) {
+  return qd_conv_wgrad_slabs(layer, xin, st_prev, dh, dh_bf16, z, st, slab, N, E, B, H, W, chunks, spb, bnb, nullptr,
+                             nullptr, stream);
 }
 
 // wgrad + dgrad of a 32-channel layer in ONE launch (bf16 dh and dx; see conv3x3_wd_kernel).  Arguments
@@ -3059,22 +3255,32 @@ QD_API int qd_conv_wgrad_dgrad(const uint16_t* xin, const float* st_prev, const 
 // per sample (see conv3x3_bwd_kernel).  zprev / st_prev: the previous layer's pre-BN output and its
 // records (x = BN+ReLU(zprev)); wt: dgrad B fragments; part: (U, chunks, 2, EC); slab rows as
 // qd_conv_wgrad's with the same chunking.
-QD_API int qd_conv_bwd_fused(const uint16_t* zprev, const float* st_prev, const uint16_t* dh, const uint16_t* z,
-                             const float* st, float* slab, const uint16_t* w, uint16_t* dx, float* part, int N, int E,
-                             int B, int H, int W, int chunks, int spb, const BnBwd* bnb, const qd::LossFinish* lf,
-                             void* stream) {
+// hosted (nullable): slab jobs served by extra grid rows of this launch (see qd_conv_wgrad_slabs)
+QD_API int qd_conv_bwd_fused_slabs(const uint16_t* zprev, const float* st_prev, const uint16_t* dh, const uint16_t* z,
+                                   const float* st, float* slab, const uint16_t* w, uint16_t* dx, float* part, int N,
+                                   int E, int B, int H, int W, int chunks, int spb, const BnBwd* bnb,
+                                   const qd::LossFinish* lf, const HostedSlabs* hosted, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const BnBwd bb = bnb ? *bnb : BnBwd{};
   const qd::LossFinish lff = lf ? *lf : qd::LossFinish{};
   if (chunks * spb < B || N % B) return (int)hipErrorInvalidValue;
-  dim3 grid((N / B) * chunks, E + (lf ? 1 : 0));
+  HostedSlabs hs;
+  if (!hosted_prepare(hosted, (N / B) * chunks, hs)) return (int)hipErrorInvalidValue;
+  dim3 grid((N / B) * chunks, E + (lf ? 1 : 0) + hs.rows_y);
   QD_GEOM(WW, {
     const size_t sm = BwdGeo<WW>::SMEM;
     if (hipError_t e = qd::allow_lds(conv3x3_bwd_kernel<WW>, sm)) return (int)e;
     hipLaunchKernelGGL((conv3x3_bwd_kernel<WW>), grid, dim3(256), sm, s, zprev, st_prev, dh, z, st, slab, w, dx, part,
-                       E, B, chunks, spb, bb, lff);
+                       E, B, chunks, spb, bb, lff, hs);
   })
   return (int)hipGetLastError();
+}
+QD_API int qd_conv_bwd_fused(const uint16_t* zprev, const float* st_prev, const uint16_t* dh, const uint16_t* z,
+                             const float* st, float* slab, const uint16_t* w, uint16_t* dx, float* part, int N, int E,
+                             int B, int H, int W, int chunks, int spb, const BnBwd* bnb, const qd::LossFinish* lf,
+                             void* stream) {
+  return qd_conv_bwd_fused_slabs(zprev, st_prev, dh, z, st, slab, w, dx, part, N, E, B, H, W, chunks, spb, bnb, lf,
+                                 nullptr, stream);
 }
 
 // qd_conv_bwd_fused at P128 on the software-pipelined kernel (conv3x3_bwd_db_kernel): same arguments and outputs

@@ -53,6 +53,21 @@ class Knobs:
     # them last (profiles/r5_19_adam_slabs_ab_v*.txt); the slab-fed variant needs 90 VGPRs (occupancy 5 for the
     # HBM-bound update instead of 7)
     adam_slabs: bool = False
+    # (world 1) the step's gradient slab reductions ride in launches that are on the HDCE chain anyway (conv.hip
+    # HostedSlabs: extra workgroups that run slab_rows_sum4_body on slabs earlier launches completed -- bit-identical,
+    # no cross-workgroup wait): layer 3's weight slab in layer 2's fused backward, layer 2's weight slab and the BN /
+    # FC-bias partials in layer 1's weight gradient, layer 1's own slab in the update (AdamSlabs, 27 workgroups); the
+    # slab-reduction launch leaves the chain: 0.3689-0.3706 against 0.3718-0.3748 ms.  slabs_hosted_first: the slab
+    # workgroups first in block order -- no gain, 0.3860-0.3875 against 0.3811-0.3829 last
+    # (profiles/r7_fused_gather_hosted_slabs_ab.txt)
+    slabs_hosted: bool = True
+    slabs_hosted_first: bool = False
+    # (world 1, stream_mode "indep") the HDCE chain's batch gather inside the conv layer-1 kernels (conv.hip GatherSrc /
+    # RowSrc): the forward reads the pilots from the HBM store and writes rowoff / rowden, the weight gradient re-reads
+    # them through rowoff; the gather launch and the x1 copy leave the chain (the replay's first step keeps its
+    # gather: the QSC stream forks from it).  Bit-identical; on top of slabs_hosted 0.3647-0.3668 against 0.3689-0.3706
+    # ms, alone 0.3718-0.3729 against 0.3724-0.3764 (same file)
+    gather_in_conv: bool = True
     # the conv stack's training forward as one persistent launch (conv.hip conv_fwd_stack_kernel; else 3 conv launches
     # + the BN tail launch).  Measured slower: 105 against 58 us alone (docs/CONCURRENCY.md)
     conv_stack: bool = False

@@ -169,6 +169,21 @@ class ConvStackHIP:
         # (bwd_fused off) wgrad + dgrad of layers 3 and 2 as one launch each
         self.fuse_wd = True
         self._bwdf = nat.fn(L, "qd_conv_bwd_db" if self.bwd_db else "qd_conv_bwd_fused", [_p] * 9 + [_i] * 7 + [_p, _p, _p])
+        # the same launches with slab reductions in extra workgroups (HostedSlabs): set by the owner of a world-1
+        # step (KNOBS.slabs_hosted) -- backward() then runs every queued reduction whose slab is complete inside
+        # layer 2's fused backward (layer 3's weight slab) and layer 1's weight gradient (layer 2's weight slab, the
+        # BN and FC-bias partials), and leaves only layer 1's own slab on the caller's batch
+        self.host_slabs = False
+        self.host_first = bool(KNOBS.slabs_hosted_first)
+        self._bwdf_s = nat.fn(L, "qd_conv_bwd_fused_slabs", [_p] * 9 + [_i] * 7 + [_p, _p, _p, _p])
+        self._wgrad_s = nat.fn(L, "qd_conv_wgrad_slabs", [_i, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i,
+                                                           _p, _p, _p, _p])
+        # the batch gather inside layer 1 (ops.gather.StepGather.in_conv: its (GatherSrc, RowSrc), set by the owner
+        # before a training forward, None = read x1): the forward reads the pilots from the store and writes rowoff /
+        # rowden, the weight gradient re-reads them through rowoff -- conv3x3_kernel's per-layer path only
+        self.gather_src = None
+        self._gsrc = None
+        self._fwd_g = nat.fn(L, "qd_conv_fwd_gather", [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p])
         # layer 3's BN backward partials from the FC data gradient's epilogue (enable_dgrad_bnred): 0 = own launch
         self.bnred_mt = 0
         self._fwd8 = nat.fn(L, "qd_conv_fwd_f8", [_p] * 4 + [_i] * 7 + [_p] * 6)
@@ -230,6 +245,9 @@ class ConvStackHIP:
         m, st = self.m, nat.stream_ptr(x1.device)
         assert x1.shape == (self.N, 2 * self.E, self.H, self.W) and x1.dtype == torch.float32 and x1.is_contiguous()
         self.x1 = x1
+        self._gsrc = self.gather_src if training else None
+        if self._gsrc is not None and (self.stack or self.fwd_split or self.l1_split):
+            raise RuntimeError("the gather inside layer 1 is conv3x3_kernel's (no conv_stack / conv_fwd_split / conv_l1_split)")
         if not self.pack_at_tail:
             self.pack_weights(st)
         hook = self.stage_hook
@@ -252,7 +270,11 @@ class ConvStackHIP:
                 bnf = BnFwd(nat.ptr(self.stats[j]), nat.ptr(m.bn_w[j]), nat.ptr(m.bn_b[j]), nat.ptr(m.run_mean[j]),
                             nat.ptr(m.run_var[j]), nat.ptr(self.st[j]), self.chunks_f, float(self.B * self.HW),
                             m.momentum, m.eps, int(training))
-            if self.l1_split and k == 0:
+            if k == 0 and self._gsrc is not None:
+                nat.check(self._fwd_g(ctypes.byref(self._gsrc[0]), nat.ptr(self.wpk[0]), nat.ptr(self.z[0]),
+                                      nat.ptr(self.stats[0]), self.N, self.E, self.B, self.H, self.W, self.chunks,
+                                      self.spw, st), "conv_fwd_gather")
+            elif self.l1_split and k == 0:
                 nat.check(self._fwd_split(1, nat.ptr(inp), None, nat.ptr(self.wpk[0]), nat.ptr(self.z[0]),
                                           nat.ptr(self.stats[0]), self.N, self.E, self.B, self.H, self.W, self.chunks,
                                           12, None, st), "conv_fwd_split1")
@@ -346,6 +368,18 @@ class ConvStackHIP:
         main = torch.cuda.current_stream(dh3.device) if side is not None else None
         dh, dh_bf = dh3, int(dh3.dtype == torch.bfloat16)
         side_used = False
+        # hosted slab reductions (host_slabs): the fused bf16 backward on one stream, a batch to take the rest
+        host = bool(self.host_slabs and slabs is not None and self.bwd_fused and not self.bwd_db and dh_bf
+                    and side is None)
+        EC = self.EC
+
+        def bn_jobs(b: SlabBatch, j: int) -> None:
+            R = self.U * self.rchunks[j]
+            b.add(self.rslab[j], m.bn_b[j].grad, 1, R, EC, ld=2 * EC)              # dbeta = sum g
+            b.add(self.rslab[j], m.bn_w[j].grad, 1, R, EC, ld=2 * EC, offset=EC)   # dgamma = sum g*xhat
+
+        # (the forward gathered inside layer 1: its weight gradient reads the pilots through rowoff, not x1)
+        rows = ctypes.byref(self._gsrc[1]) if self._gsrc is not None else None
         for k in (2, 1, 0):
             z, bst = self.z[k], self.st[k]
             rs = self.rslab[k]
@@ -363,12 +397,37 @@ class ConvStackHIP:
             # (the fused kernel has no separate weight-gradient launch to put on ``side``)
             if k > 0 and self.bwd_fused and dh_bf:
                 dx = self.dx[k - 1]
+                if host and k == 1:
+                    # layer 3's weight slab (complete since the previous launch) rides in this one
+                    hb = SlabBatch()
+                    hb.add(self.wslab[2], m.conv_w[2].grad, self.E, self.wslab[2].shape[1], self.wslab[2].shape[2])
+                    hs = hb.hosted(accumulate, self.host_first)
+                    nat.check(self._bwdf_s(nat.ptr(xin), _ptr(st_prev), nat.ptr(dh), nat.ptr(z), nat.ptr(bst),
+                                           nat.ptr(ws), nat.ptr(self.wpk_t[k]), nat.ptr(dx), nat.ptr(self.rslab[k - 1]),
+                                           self.N, self.E, self.B, self.H, self.W, self.chunks_wl[k], self.spb_wl[k],
+                                           ctypes.byref(bnb), lf, ctypes.byref(hs), st), f"conv_bwd_fused_slabs{k + 1}")
+                    dh, dh_bf = dx, 1
+                    continue
                 nat.check(self._bwdf(nat.ptr(xin), _ptr(st_prev), nat.ptr(dh), nat.ptr(z), nat.ptr(bst), nat.ptr(ws),
                                      nat.ptr(self.wpk_t[k]), nat.ptr(dx), nat.ptr(self.rslab[k - 1]), self.N, self.E,
                                      self.B, self.H, self.W, self.chunks_wl[k], self.spb_wl[k], ctypes.byref(bnb), lf,
                                      st), f"conv_bwd_fused{k + 1}")
                 dh, dh_bf = dx, 1
                 continue
+            if host:
+                # layer 1's weight gradient hosts what the caller queued (the FC bias partials), layer 2's weight
+                # slab and every BN partial: all complete before this launch; its own slab stays on the batch
+                assert lf is None and k == 0
+                slabs.add(self.wslab[1], m.conv_w[1].grad, self.E, self.wslab[1].shape[1], self.wslab[1].shape[2])
+                for j in range(3):
+                    bn_jobs(slabs, j)
+                hs = slabs.hosted(accumulate, self.host_first)
+                nat.check(self._wgrad_s(1, nat.ptr(xin), None, nat.ptr(dh), dh_bf, nat.ptr(z), nat.ptr(bst),
+                                        nat.ptr(ws), self.N, self.E, self.B, self.H, self.W, self.chunks_wl[0],
+                                        self.spb_wl[0], ctypes.byref(bnb), ctypes.byref(hs), rows, st),
+                          "conv_wgrad_slabs1")
+                slabs.add(ws, m.conv_w[0].grad, self.E, ws.shape[1], ws.shape[2])
+                return
             assert lf is None, "the deferred loss finish needs layer 3's fused backward launch"
             if k > 0 and self.fuse_wd and dh_bf and self.dx_bf16 and side is None:
                 # weight AND data gradient of this layer in one launch (independent: side by side)
@@ -386,9 +445,10 @@ class ConvStackHIP:
                 side.wait_stream(main)
                 side_used = True
             wst = nat.stream_ptr(dh3.device) if not on_side else ctypes.c_void_p(side.cuda_stream)
-            nat.check(self._wgrad(k + 1, nat.ptr(xin), _ptr(st_prev), nat.ptr(dh), dh_bf, nat.ptr(z), nat.ptr(bst),
-                                  nat.ptr(ws), self.N, self.E, self.B, self.H, self.W, self.chunks_wl[k], self.spb_wl[k],
-                                  ctypes.byref(bnb), wst), f"conv_wgrad{k + 1}")
+            nat.check(self._wgrad_s(k + 1, nat.ptr(xin), _ptr(st_prev), nat.ptr(dh), dh_bf, nat.ptr(z), nat.ptr(bst),
+                                    nat.ptr(ws), self.N, self.E, self.B, self.H, self.W, self.chunks_wl[k],
+                                    self.spb_wl[k], ctypes.byref(bnb), None, rows if k == 0 else None, wst),
+                      f"conv_wgrad{k + 1}")
             if k > 0:
                 dx = self.dx[k - 1]
                 # ... and the previous layer's BN backward reduction fused into this dgrad's epilogue
@@ -405,12 +465,9 @@ class ConvStackHIP:
         # for every slab reduction of the step phase) or launched here
         own = slabs is None
         batch = SlabBatch() if own else slabs
-        EC = self.EC
         for k in range(3):
             w = self.wslab[k]
-            R = self.U * self.rchunks[k]
             batch.add(w, m.conv_w[k].grad, self.E, w.shape[1], w.shape[2])
-            batch.add(self.rslab[k], m.bn_b[k].grad, 1, R, EC, ld=2 * EC)              # dbeta = sum g
-            batch.add(self.rslab[k], m.bn_w[k].grad, 1, R, EC, ld=2 * EC, offset=EC)   # dgamma = sum g*xhat
+            bn_jobs(batch, k)
         if own:
             batch.launch(accumulate, st)

@@ -21,6 +21,18 @@ from .. import _native as nat
 _p, _i, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
 
 
+class GatherSrc(ctypes.Structure):
+    """csrc/hip/conv.hip ``GatherSrc``: layer 1's forward reads the step's pilots from the store itself."""
+    _fields_ = [("perm", _p), ("cursor", _p), ("nperm", _l), ("Yp", _p), ("yp_stream_stride", _l),
+                ("lab_stream_rows", _l), ("rowpow_l", _p), ("rowpow_p", _p), ("rowoff", _p), ("rowden", _p),
+                ("scale", _p), ("plane", _i), ("off", _i), ("adv", _i)]
+
+
+class RowSrc(ctypes.Structure):
+    """csrc/hip/conv.hip ``RowSrc``: layer 1's weight gradient reads the same pilots through rowoff."""
+    _fields_ = [("rowoff", _p), ("Yp", _p), ("yp_stream_stride", _l), ("lab_stream_rows", _l), ("plane", _i)]
+
+
 class StepGather:
     def __init__(self, E: int, U: int, B: int, H: int, W: int, device, with_classifier: bool = True):
         self.E, self.U, self.B, self.H, self.W = E, U, B, H, W
@@ -40,6 +52,32 @@ class StepGather:
         self.off, self.adv = 0, B
         self.den_scale = None
         self.den_global = None   # (S, 2): the global batch's per-stream label / perf powers (the torch NMSE's form)
+        # (in_conv) the HDCE half left to the conv kernels: (GatherSrc, RowSrc) of the step's batch, else None
+        self.fused = None
+
+    def in_conv(self, store, perm: torch.Tensor, cursor: torch.Tensor) -> None:
+        """The HDCE half of ``from_cursor`` WITHOUT a launch: ``self.fused`` = the (GatherSrc, RowSrc) with which
+        layer 1's forward reads batch ``perm[*cursor : *cursor + B]`` from the store and writes rowoff / rowden, and
+        its weight gradient re-reads the pilots through rowoff (ConvStackHIP).  x1 is not written.  The cursor is
+        only read: the caller advances it later in the step.  GPU, with ``rowpow`` set, weak scaling."""
+        Yp, HL = store.Yp, store.Hlabel
+        cols = HL.shape[-1]
+        assert Yp.is_cuda and self.rowpow is not None and self.den_scale is None and self.off == 0
+        assert perm.dtype == torch.int64 and cursor.dtype == torch.int32 and perm.numel() == Yp.shape[1]
+        assert Yp.dtype == torch.float32 and Yp[0, 0].is_contiguous() and Yp.stride(1) == self.plane
+        assert HL.stride(1) == cols and HL.stride(0) % cols == 0 and store.Hperf.stride() == HL.stride()
+        g = GatherSrc()
+        g.perm, g.cursor, g.nperm = perm.data_ptr(), cursor.data_ptr(), perm.numel()
+        g.Yp, g.yp_stream_stride, g.lab_stream_rows = Yp.data_ptr(), Yp.stride(0), HL.stride(0) // cols
+        g.rowpow_l = self.rowpow[0].data_ptr()
+        g.rowpow_p = self.rowpow[1].data_ptr() if self.rowpow[1] is not None else None
+        g.rowoff, g.rowden, g.scale = self.rowoff.data_ptr(), self.rowden.data_ptr(), None
+        g.plane, g.off, g.adv = self.plane, self.off, self.adv
+        r = RowSrc()
+        r.rowoff, r.Yp, r.yp_stream_stride, r.lab_stream_rows, r.plane = (g.rowoff, g.Yp, g.yp_stream_stride,
+                                                                          g.lab_stream_rows, g.plane)
+        self.fused = (g, r)
+        self._fused_keep = (perm, cursor, Yp)   # (the struct holds raw pointers)
 
     def set_part(self, off: int, global_batch: int) -> None:
         """(strong scaling) take rows [off, off + B) of every global batch of ``global_batch`` rows per stream."""
@@ -60,6 +98,8 @@ class StepGather:
         Yp, HL = store.Yp, store.Hlabel
         assert perm.dtype == torch.int64 and cursor.dtype == torch.int32
         assert done is None or done.dtype == torch.int32
+        if hdce:
+            self.fused = None
         cols = HL.shape[-1]
         if Yp.is_cuda:
             assert Yp.dtype == torch.float32 and Yp[0, 0].is_contiguous() and Yp.stride(1) == self.plane
@@ -132,6 +172,7 @@ class StepGather:
 
     def __call__(self, store, idx: torch.Tensor) -> None:
         Yp, HL = store.Yp, store.Hlabel
+        self.fused = None
         S, N = Yp.shape[:2]
         assert S == self.S and idx.shape == (self.B,) and idx.dtype == torch.int64
         assert Yp.dtype == torch.float32 and Yp[0, 0].is_contiguous() and Yp.stride(1) == self.plane

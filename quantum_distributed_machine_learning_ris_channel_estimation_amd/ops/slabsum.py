@@ -19,6 +19,18 @@ _p, _i = ctypes.c_void_p, ctypes.c_int
 MAX_JOBS = 16
 
 
+class SlabJobsArg(ctypes.Structure):
+    """csrc/hip/conv.hip ``SlabJobs``."""
+    _fields_ = [("slab", _p * MAX_JOBS), ("out", _p * MAX_JOBS), ("groups", _i * MAX_JOBS), ("rows", _i * MAX_JOBS),
+                ("width", _i * MAX_JOBS), ("ld", _i * MAX_JOBS), ("vec", _i * MAX_JOBS), ("accumulate", _i)]
+
+
+class HostedSlabs(ctypes.Structure):
+    """csrc/hip/conv.hip ``HostedSlabs``: slab jobs that ride in extra workgroups of a conv backward launch (the
+    launcher derives wg0 / rows_y / vec)."""
+    _fields_ = [("jobs", SlabJobsArg), ("wg0", _i * (MAX_JOBS + 1)), ("n", _i), ("rows_y", _i), ("first", _i)]
+
+
 class SlabBatch:
     def __init__(self):
         self.jobs: List[Tuple[int, torch.Tensor, int, int, int, int]] = []
@@ -48,6 +60,19 @@ class SlabBatch:
             out.append((slab_ptr, off - lo, groups, rows, width, ld))
         self.jobs = []
         return out
+
+    def hosted(self, accumulate: bool, first: bool = False) -> "HostedSlabs":
+        """The queued reductions as the ``HostedSlabs`` argument of a conv backward launch that runs them in extra
+        workgroups (ConvStackHIP.backward); the whole batch is consumed (nothing is launched here).  Every slab must
+        be complete before that launch starts."""
+        h = HostedSlabs()
+        h.n, h.first, h.jobs.accumulate = len(self.jobs), int(first), int(accumulate)
+        self._held = [j[1] for j in self.jobs]   # (the outputs stay alive until the next batch)
+        for k, (slab_ptr, o, groups, rows, width, ld) in enumerate(self.jobs):
+            h.jobs.slab[k], h.jobs.out[k] = slab_ptr, o.data_ptr()
+            h.jobs.groups[k], h.jobs.rows[k], h.jobs.width[k], h.jobs.ld[k] = groups, rows, width, ld
+        self.jobs = []
+        return h
 
     def launch(self, accumulate: bool, stream) -> None:
         if not self.jobs:

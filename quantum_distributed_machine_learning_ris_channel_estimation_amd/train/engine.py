@@ -392,6 +392,8 @@ class HDCEStep:
     def forward_fc(self, Yp: torch.Tensor, HL: torch.Tensor, HP: torch.Tensor) -> torch.Tensor:
         """From stream-major tensors Yp (E,U,B,2,H,W), HL/HP (E,U,B,2048)."""
         self.nmse.rowoff = None
+        if self.hip:
+            self.conv.gather_src = None
         x1 = self.m.pack_input(Yp).float().contiguous()
         return self._forward_fc(x1, HDCEModel.rows_from_streams(HL), HDCEModel.rows_from_streams(HP))
 
@@ -401,6 +403,8 @@ class HDCEStep:
         self.nmse.rowoff = g.rowoff
         self._rowden = g.rowden if getattr(g, "rowpow", None) is not None else None
         self._apply_den_global()
+        if self.hip:   # (StepGather.in_conv: layer 1 gathers the batch itself and writes rowoff / rowden)
+            self.conv.gather_src = getattr(g, "fused", None)
         return self._forward_fc(g.x1, store.Hlabel, store.Hperf)
 
     def _apply_den_global(self) -> None:
@@ -422,6 +426,7 @@ class HDCEStep:
         self._rowden = g.rowden if getattr(g, "rowpow", None) is not None else None
         self._apply_den_global()
         self.conv.stage_hook = self.stage_hook
+        self.conv.gather_src = getattr(g, "fused", None)
         self._A_conv = self.conv.forward(g.x1, training=True)
         if self.stage_hook is not None:
             self.stage_hook("conv")

@@ -318,9 +318,27 @@ class FlagshipTrainer(DPPlan):
         self.adam_slabs = bool(KNOBS.adam_slabs and self.hstep.hip and ctx.world == 1 and not cfg.split_graphs
                                and self.hstep.writes_grads and self.hopt.kind in ("adam", "adamw")
                                and len(self.hopt.bounds) == 1 and not self.fused_adam)
+        # (world 1) ... or only layer 1's weight slab, the one produced last: every other slab reduction rides in a
+        # conv backward launch (ConvStackHIP.host_slabs, KNOBS.slabs_hosted)
+        self.slabs_hosted = bool(KNOBS.slabs_hosted and self.hstep.hip and ctx.world == 1 and not cfg.split_graphs
+                                 and self.hstep.writes_grads and self.hopt.kind in ("adam", "adamw")
+                                 and len(self.hopt.bounds) == 1 and not self.fused_adam
+                                 and self.hstep.conv.bwd_fused and not self.hstep.conv.bwd_db)
+        if self.slabs_hosted:
+            self.hstep.conv.host_slabs = True
+        # (hosted: only where the update follows the conv backward at once -- _hdce_backward; a backward_conv() on
+        # its own, as in the serial plan's graphs, reduces layer 1's slab in a small launch of its own)
+        self.slabs_in_update = self.adam_slabs or self.slabs_hosted   # the update takes what _hdce_backward left
         self.hstep.defer_slabs = self.adam_slabs
         # end-of-step weight pack (GPU fused path)
         self.tail_pack = bool(self.hstep.hip and cfg.tail_pack)
+        # the HDCE chain's own gather (indep plan: it writes only x1, rowoff and rowden, and the update advances the
+        # cursor) inside the conv layer-1 kernels (KNOBS.gather_in_conv).  Strong scaling keeps the gather launch.
+        cv = self.hstep.conv if self.hstep.hip else None
+        self.gather_in_conv = bool(KNOBS.gather_in_conv and cv is not None and dev.type == "cuda" and mode == "indep"
+                                   and ctx.world == 1 and not cfg.split_graphs and self.tail_pack
+                                   and self.gat.rowpow is not None and not self.strong and self.gat.den_scale is None
+                                   and not (cv.stack or cv.fwd_split or cv.l1_split) and cv.spw <= 64)
         if self.tail_pack:
             self.hstep.conv.pack_at_tail = True
             self._tail_pack_launch(advance=False)   # the first step's images
@@ -405,7 +423,7 @@ class FlagshipTrainer(DPPlan):
         for n in names:
             cur.wait_stream(self.streams[n])
 
-    def _gather(self, hdce: bool = True, classifier: bool = True) -> None:
+    def _gather(self, hdce: bool = True, classifier: bool = True, in_conv: bool = False) -> None:
         # the fused GPU kernels WRITE every gradient (one producer per element): no zero_grad fills
         if hdce and not self.hstep.writes_grads:
             self.hdce.space.zero_grad()
@@ -415,6 +433,10 @@ class FlagshipTrainer(DPPlan):
         # end-of-step weight pack (tail_pack) the pack advances cur[0]; else the gather itself does
         k = 0 if hdce else 1
         advance = not (self.tail_pack and k == 0)
+        if in_conv:   # (gather_in_conv) no launch: layer 1's kernels read the batch at cur[0] themselves
+            assert hdce and not classifier and not advance
+            self.gat.in_conv(self.store, self.perm, self.cur[0, 0:1])
+            return
         self.gat.from_cursor(self.store, self.perm, self.cur[k, 0:1], self.cur_done[k, 0:1] if advance else None,
                              hdce=hdce, classifier=classifier)
 
@@ -459,14 +481,21 @@ class FlagshipTrainer(DPPlan):
         self._hdce_forward()
         self._hdce_backward_update()
 
+    def _hdce_backward(self) -> None:
+        """conv/BN backward whose unreduced slabs the next _hdce_update takes (slabs_in_update)."""
+        keep = self.hstep.defer_slabs
+        self.hstep.defer_slabs = self.slabs_in_update
+        self.hstep.backward_conv()
+        self.hstep.defer_slabs = keep
+
     def _hdce_backward_update(self) -> None:
         """conv/BN backward + the one Adam launch over the whole HDCE space (+ the conv weight images)."""
-        self.hstep.backward_conv()
+        self._hdce_backward()
         self._hdce_update()
 
     def _hdce_update(self) -> None:
         pk = self._adam_pack()
-        sl = self.hstep.take_slabs() if self.adam_slabs else None
+        sl = self.hstep.take_slabs() if self.slabs_in_update else None
         self.hopt.step(grad_scale=1.0, skip=self.hskip, pack=pk, slabs=sl)
         if self.tail_pack and pk is None:
             self._tail_pack_launch()
@@ -486,7 +515,7 @@ class FlagshipTrainer(DPPlan):
             with self._fork(self.streams["qsc"]):
                 self._qsc_branch(with_opt=True)
             self._hdce_forward()
-            self.hstep.backward_conv()
+            self._hdce_backward()
             self._join(("qsc", "fc") if self.fc_adam_side else ("qsc",))
             self._hdce_update()
             return
@@ -501,7 +530,8 @@ class FlagshipTrainer(DPPlan):
         stream only (round 3's independent plans shared the gather's output across the streams: that race is why
         they were not reproducible).  ``first``: the replay's first step orders the qsc stream after this step's
         first node (a branch forked before any node would be a root of the graph)."""
-        self._gather(classifier=False)
+        # (the replay's first step keeps the gather launch: the qsc stream forks from that node)
+        self._gather(classifier=False, in_conv=self.gather_in_conv and not first)
         q = self.streams["qsc"]
         after_conv = (self.cfg.qsc_start == "conv" or self.fc_adam_next) and self.hstep.hip
         if after_conv:
@@ -519,7 +549,7 @@ class FlagshipTrainer(DPPlan):
                 self.hloss.copy_(loss)
         else:
             self._hdce_forward()
-        self.hstep.backward_conv()
+        self._hdce_backward()
         self._hdce_update()
         if self.fc_adam_next:
             with self._fork(self.streams["fc"]):

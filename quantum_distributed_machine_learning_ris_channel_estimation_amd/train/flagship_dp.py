@@ -88,8 +88,8 @@ class DPPlan:
 
     def _dp_gr(self) -> None:
         pk = self._adam_pack()
-        # (world-1 serial plan with adam_slabs: the update sums the step's gradient slabs itself)
-        sl = self.hstep.take_slabs() if getattr(self, "adam_slabs", False) else None
+        # (world-1 serial plan with adam_slabs / slabs_hosted: the update sums the gradient slabs left to it itself)
+        sl = self.hstep.take_slabs() if getattr(self, "slabs_in_update", False) else None
         self.hopt.step(grad_scale=self._hgs, skip=self.hskip, part=0 if len(self.hopt.bounds) > 1 else None, pack=pk,
                        slabs=sl)
         if self.tail_pack and pk is None:
