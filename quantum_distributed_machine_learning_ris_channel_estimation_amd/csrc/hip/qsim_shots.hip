@@ -16,228 +16,10 @@
 //                       hi32(seed))), c = ctr0 + (counter ? *counter : 0)
 //   t = (uint64(r) * T) >> 32; outcome k = the smallest index with cum[k] > t (never a zero-probability outcome)
 //   c1[i] = shots whose outcome has bit i set;  E[b, i] = (float)(shots - 2 c1[i]) / (float)shots
-#include "common.h"
+#include "qsim_shots_dev.h"
 
 namespace qd {
 namespace qshots {
-
-struct cf {
-  float x, y;
-};
-__device__ __forceinline__ cf cmul(cf a, cf b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-
-constexpr int NT = 256;
-constexpr int NW = NT / 64;
-constexpr int kMaxQubits = 12;
-constexpr int kMaxShots = 1 << 20;
-
-// LDS carve (bytes): trig (<= 12 float4) | wave totals of the scan (NW) | per-wave bit counts (NW x 12) | data: the
-// state (2^n complex), or the CDF (2^n words + pads: never larger) -- in the fused kernel one after the other
-constexpr int O_TRIG = 0, O_WTOT = 256, O_WCNT = 272, O_DATA = 512;
-
-// CDF word of outcome k: one pad word per 32, so the scan's 16-word chunks (n = 12) fall on different banks
-__device__ __host__ __forceinline__ constexpr int cdf_at(int k) { return k + (k >> 5); }
-template <int N>
-constexpr int cdf_bytes() {
-  return (cdf_at((1 << N) - 1) + 1) * 4;
-}
-template <int N>
-constexpr size_t smem_bytes(bool state) {
-  static_assert(cdf_bytes<N>() <= (int)sizeof(cf) * (1 << N), "the CDF fits over the state");
-  return O_DATA + (state ? sizeof(cf) * (1 << N) : cdf_bytes<N>());
-}
-
-template <int N>
-__device__ __forceinline__ int ring_inv(int k) {
-  k ^= (k >> (N - 1)) & 1;
-#pragma unroll
-  for (int i = N - 2; i >= 0; --i) k ^= ((k >> i) & 1) << (i + 1);
-  return k;
-}
-
-// (cos, sin) of theta/2 and (cos, sin) of phi/2 of one layer's qubits, into LDS
-__device__ __forceinline__ void layer_trig(float4* trig, const float* wl, const float* xs, int n) {
-  if (threadIdx.x < n) {
-    const int q = threadIdx.x;
-    float s, c, sp, cp;
-    __sincosf(0.5f * (wl[2 * q] + (xs ? xs[q] : 0.f)), &s, &c);
-    __sincosf(0.5f * wl[2 * q + 1], &sp, &cp);
-    trig[q] = make_float4(c, s, cp, sp);
-  }
-}
-
-// RZ(phi) RY(theta) on the pair (a0: bit 0, a1: bit 1)
-__device__ __forceinline__ void gate_fwd(cf& a0, cf& a1, float4 t) {
-  const cf t0 = {t.x * a0.x - t.y * a1.x, t.x * a0.y - t.y * a1.y};
-  const cf t1 = {t.y * a0.x + t.x * a1.x, t.y * a0.y + t.x * a1.y};
-  a0 = cmul(t0, cf{t.z, -t.w});
-  a1 = cmul(t1, cf{t.z, t.w});
-}
-
-// The circuit's final state of one sample, in A (LDS).
-template <int N>
-__device__ void build_state(cf* A, float4* trig, const float* xs, const float* w, int L) {
-  constexpr int D = 1 << N;
-  constexpr int PER = D >= NT ? D / NT : 1;   // amplitudes per thread of the ring pass
-  layer_trig(trig, w, xs, N);
-  __syncthreads();
-  // embedding + layer 0 + ring: the product state gathered through f^-1
-  for (int j = threadIdx.x; j < D; j += NT) {
-    const int k = ring_inv<N>(j);
-    cf a = {1.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-      const float4 t = trig[q];
-      a = cmul(a, ((k >> q) & 1) ? cf{t.y * t.z, t.y * t.w} : cf{t.x * t.z, -t.x * t.w});
-    }
-    A[j] = a;
-  }
-  __syncthreads();
-  for (int l = 1; l < L; ++l) {
-    layer_trig(trig, w + 2 * N * l, nullptr, N);
-    __syncthreads();
-    // pair sweeps, up to three qubits per LDS round trip: a thread owns the 2^NB amplitudes that differ in the
-    // group's bits (the layer's gates act on different wires, so they commute)
-    static_for<0, (N + 2) / 3>([&](auto gc) {
-      constexpr int g0 = 3 * decltype(gc)::value;
-      constexpr int NB = (N - g0) < 3 ? (N - g0) : 3;
-      for (int t = threadIdx.x; t < (D >> NB); t += NT) {
-        const int base = ((t >> g0) << (g0 + NB)) | (t & ((1 << g0) - 1));
-        cf a[1 << NB];
-#pragma unroll
-        for (int j = 0; j < (1 << NB); ++j) a[j] = A[base | (j << g0)];
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const float4 tg = trig[g0 + b];
-#pragma unroll
-          for (int j = 0; j < (1 << NB); ++j)
-            if (!((j >> b) & 1)) gate_fwd(a[j], a[j | (1 << b)], tg);
-        }
-#pragma unroll
-        for (int j = 0; j < (1 << NB); ++j) A[base | (j << g0)] = a[j];
-      }
-      __syncthreads();
-    });
-    // the CNOT ring, in place: A'[j] = A[f^-1(j)], every thread's amplitudes in registers across one barrier
-    cf a[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int j = threadIdx.x + i * NT;
-      if (j < D) a[i] = A[ring_inv<N>(j)];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int j = threadIdx.x + i * NT;
-      if (j < D) A[j] = a[i];
-    }
-    __syncthreads();
-  }
-}
-
-// |amp|^2 with explicit roundings: the probabilities kernel and the fused kernel form the same fp32 value
-__device__ __forceinline__ float prob_of(cf a) { return __fmaf_rn(a.x, a.x, __fmul_rn(a.y, a.y)); }
-
-__device__ __forceinline__ uint32_t quantise(float p) { return p > 0.f ? __float2uint_rn(p * 1073741824.f) : 0u; }
-
-// Inclusive prefix sum of the D quantised words in cdf (in place); returns T.  Every thread of the block calls it;
-// the words must have been written before the call (it starts with a barrier).
-template <int N>
-__device__ uint32_t cdf_scan(uint32_t* cdf, uint32_t* wtot) {
-  constexpr int D = 1 << N;
-  constexpr int CH = D >= NT ? D / NT : 1;   // words per thread (threads >= D own none)
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();
-  const bool own = threadIdx.x * CH < D;
-  uint32_t run = 0;
-  if (own) {
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-      run += cdf[cdf_at(threadIdx.x * CH + j)];
-      cdf[cdf_at(threadIdx.x * CH + j)] = run;
-    }
-  }
-  uint32_t v = run;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t u = __shfl_up(v, d);
-    if (lane >= d) v += u;
-  }
-  if (lane == 63) wtot[wv] = v;
-  __syncthreads();
-  uint32_t off = v - run;
-  for (int k = 0; k < wv; ++k) off += wtot[k];
-  if (own) {
-#pragma unroll
-    for (int j = 0; j < CH; ++j) cdf[cdf_at(threadIdx.x * CH + j)] += off;
-  }
-  __syncthreads();
-  return cdf[cdf_at(D - 1)];
-}
-
-struct Philox {
-  uint32_t c[4];
-};
-__device__ __forceinline__ Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                                uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0;
-    c1 = l1;
-    c2 = h0 ^ c3 ^ k1;
-    c3 = l0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return {{c0, c1, c2, c3}};
-}
-
-// Draw `shots` outcomes of sample b from the scanned CDF and write E (and counts).  Every thread calls it.
-template <int N>
-__device__ void sample_counts(const uint32_t* cdf, uint32_t T, uint32_t* wcnt, float* __restrict__ E,
-                              int* __restrict__ counts, int b, int shots, unsigned long long seed,
-                              unsigned long long ctr) {
-  constexpr int D = 1 << N;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t acc[N];   // wave-uniform
-#pragma unroll
-  for (int i = 0; i < N; ++i) acc[i] = 0;
-  const uint32_t nblk = ((uint32_t)shots + 3u) >> 2;   // Philox blocks: four shots each
-  for (uint32_t j0 = 0; j0 < nblk; j0 += NT) {
-    const uint32_t j = j0 + threadIdx.x;
-    const Philox ph = philox4x32_10(j, (uint32_t)b, (uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)seed,
-                                    (uint32_t)(seed >> 32));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const bool valid = j < nblk && 4u * j + r < (uint32_t)shots;   // lanes beyond `shots` count nothing
-      const uint32_t t = __umulhi(ph.c[r], T);
-      int k = 0;   // upper bound: the smallest k with cum[k] > t (t < T = cum[D - 1] whenever T > 0)
-#pragma unroll
-      for (int step = D >> 1; step >= 1; step >>= 1)
-        if (cdf[cdf_at(k + step - 1)] <= t) k += step;
-#pragma unroll
-      for (int i = 0; i < N; ++i) acc[i] += (uint32_t)__popcll(__ballot(valid && ((k >> i) & 1)));
-    }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) wcnt[wv * N + i] = acc[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < N) {
-    int c1 = 0;
-#pragma unroll
-    for (int k = 0; k < NW; ++k) c1 += (int)wcnt[k * N + threadIdx.x];
-    E[(size_t)b * N + threadIdx.x] = __fdiv_rn((float)(shots - 2 * c1), (float)shots);
-    if (counts != nullptr) counts[(size_t)b * N + threadIdx.x] = c1;
-  }
-}
-
-__device__ __forceinline__ unsigned long long shot_counter(unsigned long long ctr0, const unsigned long long* counter) {
-  return ctr0 + (counter != nullptr ? *counter : 0ull);
-}
 
 // ------------------------------------------------------------------------------- kernels
 template <int N>

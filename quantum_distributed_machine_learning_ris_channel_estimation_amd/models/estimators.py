@@ -80,16 +80,24 @@ class QuantumLayer(nn.Module):
     of shape (n_layers, n_qubits, 2), maps (B, n) angles to (B, n) <Z_i> values.
 
     ``shots`` (settable; None / 0 = exact expectations) is the device's ``shots=``: every <Z_i> is then
-    estimated from that many measurement shots (ops/quantum.py ``qsim(shots=)``; gradients stay exact,
-    straight-through).  The shot stream is keyed by ``shot_seed`` and a Python-side call counter that
+    estimated from that many measurement shots (ops/quantum.py ``qsim(shots=)``; by default gradients stay
+    exact, straight-through).  The shot stream is keyed by ``shot_seed`` and a Python-side call counter that
     every forward advances, so successive calls draw different shots; ``manual_shot_seed`` restarts it.
-    Neither is a parameter or a buffer: the state_dict is that of the exact layer."""
+    Neither is a parameter or a buffer: the state_dict is that of the exact layer.
 
-    def __init__(self, n_qubits: int, n_layers: int, backend: Optional[str] = None, shots: Optional[int] = None):
+    ``diff_method`` (settable; "adjoint" or "parameter_shift") selects the backward: the exact adjoint, or the
+    parameter-shift rule measured with the same ``shots`` (``qsim(diff_method=)``).  ``shift_mask`` (settable;
+    None or a (n_layers, n_qubits, 2) bool tensor) names the parameters whose shifted circuits run; the others
+    get a zero gradient.  Both are plain attributes too."""
+
+    def __init__(self, n_qubits: int, n_layers: int, backend: Optional[str] = None, shots: Optional[int] = None,
+                 diff_method: str = "adjoint"):
         super().__init__()
         self.n_qubits, self.n_layers = n_qubits, n_layers
         self.backend = backend
         self.shots = shots
+        self.diff_method = diff_method
+        self.shift_mask = None
         self.shot_seed = 0
         self._shot_calls = 0
         self.weights = nn.Parameter(init_weights_(torch.empty(n_layers, n_qubits, 2)))
@@ -101,15 +109,16 @@ class QuantumLayer(nn.Module):
 
     def forward(self, x: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         w = self.weights if weights is None else weights
+        kw = {} if self.diff_method == "adjoint" else {"diff_method": self.diff_method, "shift_mask": self.shift_mask}
         if not self.shots:
-            return qsim(x.float(), w, self.backend)
+            return qsim(x.float(), w, self.backend, **kw)
         call = self._shot_calls
         self._shot_calls += 1
-        return qsim(x.float(), w, self.backend, shots=int(self.shots), seed=self.shot_seed, counter=call)
+        return qsim(x.float(), w, self.backend, shots=int(self.shots), seed=self.shot_seed, counter=call, **kw)
 
     def extra_repr(self) -> str:
         return (f"n_qubits={self.n_qubits}, n_layers={self.n_layers}, backend={self.backend}, shots={self.shots}, "
-                f"shot_seed={self.shot_seed}")
+                f"shot_seed={self.shot_seed}, diff_method={self.diff_method}")
 
 
 class QSC_P128(nn.Module):
@@ -127,13 +136,14 @@ class QSC_P128(nn.Module):
     ``use_quantum=False`` selects ``classical_fallback`` (referenced at E:168-170 but never
     defined there): Linear(n, n) + Tanh in place of the VQC, an equal-width classical ablation
     with the same (-1, 1) output range as <Z_i>.
-    ``shots`` goes to the ``qlayer`` (finite-shot <Z_i>; None = exact).
+    ``shots`` goes to the ``qlayer`` (finite-shot <Z_i>; None = exact), and so does ``diff_method``
+    ("adjoint", or "parameter_shift": the gradient an on-chip QNN measures).
     """
 
     def __init__(self, n_qubits: int = 6, n_layers: int = 3, n_classes: int = 3, use_quantumnat: bool = True,
                  use_gradient_pruning: bool = True, pilot_num: int = 128, backend: Optional[str] = None,
                  noise_level: float = 0.01, gradient_threshold: float = 0.1, use_quantum: bool = True,
-                 shots: Optional[int] = None):
+                 shots: Optional[int] = None, diff_method: str = "adjoint"):
         super().__init__()
         self.use_quantum = use_quantum
         self.num_qubits = n_qubits
@@ -147,7 +157,7 @@ class QSC_P128(nn.Module):
         H, W = pilot_grid(pilot_num)
         flat = 32 * (H // 4) * (W // 4)
         # registration order matters: qlayer.weights is the first state_dict key (E:149 < E:152)
-        self.qlayer = QuantumLayer(n_qubits, n_layers, backend, shots)
+        self.qlayer = QuantumLayer(n_qubits, n_layers, backend, shots, diff_method)
         self.preprocess = nn.Sequential(
             nn.Conv2d(2, 16, kernel_size=3, stride=1, padding=1),
             nn.ReLU(),

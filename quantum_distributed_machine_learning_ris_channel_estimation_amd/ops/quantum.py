@@ -19,7 +19,11 @@ Here three interchangeable backends implement the SAME function:
 
 Finite shots (``qsim(..., shots=N)``, ``qsim_probs``, ``sample_z``, ``counter_add``): <Z_i> estimated from N
 measurement shots of the final state -- csrc/hip/qsim_shots.hip (n <= 12) on ``hip``, simulate-then-sample on
-``cpu`` with the same integer sampling contract; gradients stay the exact adjoint (straight-through).
+``cpu`` with the same integer sampling contract; by default gradients stay the exact adjoint (straight-through).
+
+Parameter shift (``qsim(..., diff_method="parameter_shift")``, ``pshift_rows``): the backward an on-chip QNN can
+measure -- two more runs of the circuit per parameter, one angle shifted by +-pi/2, exact or with the forward's
+finite shots; csrc/hip/qsim_pshift.hip (n <= 12) on ``hip``, composed from ``qsim_probs`` and ``sample_z`` on ``cpu``.
 """
 from __future__ import annotations
 
@@ -425,8 +429,139 @@ class _ReplaceValue(torch.autograd.Function):
         return g, None
 
 
+# ----------------------------------------------------------------------------- parameter shift
+DIFF_METHODS = ("adjoint", "parameter_shift")
+PSHIFT_ID_SHIFT = 48   # circuit (p, s) draws under call counter c + (id << 48), id = 1 + 2p + s; the forward is id 0
+
+
+def pshift_counter(counter: int, p: int, s: int) -> int:
+    """The call counter of shifted circuit (p, s) (s = 0: +pi/2, 1: -pi/2) of a call with counter ``counter``.
+    Distinct from the forward's and from every other circuit's for counters below 2^48."""
+    return (int(counter) + ((1 + 2 * p + s) << PSHIFT_ID_SHIFT)) & _M64
+
+
+def _check_pshift_shape(n: int, L: int) -> None:
+    if 4 * n * L + 1 >= 1 << 16:
+        raise ValueError(f"parameter shift needs 2 * (2 n L) + 1 < 2^16 stream ids, got n={n} L={L}")
+
+
+def _mask_u8(shift_mask, w: torch.Tensor) -> Optional[torch.Tensor]:
+    if shift_mask is None:
+        return None
+    if tuple(shift_mask.shape) != tuple(w.shape[-3:]):
+        raise ValueError(f"shift_mask must be {tuple(w.shape[-3:])}, got {tuple(shift_mask.shape)}")
+    return (shift_mask != 0).to(device=w.device, dtype=torch.uint8).reshape(-1).contiguous()
+
+
+def hip_qsim_pshift(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, G: torch.Tensor,
+                    Epm: Optional[torch.Tensor] = None, probs: Optional[torch.Tensor] = None,
+                    mask: Optional[torch.Tensor] = None, need_dx: bool = True, shots: int = 0, seed: int = 0,
+                    ctr0: int = 0, counter_ptr=None, wgroup: int = 0) -> None:
+    """Raw launcher of csrc/hip/qsim_pshift.hip (n <= 12): G (B, P) fp32 = sum_j gE[b, j] (E+_j - E-_j) / 2 for
+    every parameter p = (l n + q) 2 + k, P = 2nL; Epm (nullable; B, P, 2, n) the shifted expectations, probs
+    (nullable; B, P, 2, 2^n) the probabilities they were measured from; mask (nullable; P) uint8, 0 = skip the
+    parameter (a layer-0 RY one still runs with ``need_dx``).  shots = 0: exact expectations."""
+    B, n = x.shape
+    f = nat.fn(nat.hip_lib(), "qd_qsim_pshift",
+               [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _u64, _u64, _p, _p])
+    opt = lambda t: nat.ptr(t) if t is not None else None   # noqa: E731
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(gE), nat.ptr(G), opt(Epm), opt(probs), opt(mask), B, n, w.shape[-3],
+                wgroup, int(need_dx), shots, seed & _M64, ctr0 & _M64, counter_ptr, nat.stream_ptr(x.device)),
+              "qd_qsim_pshift")
+
+
+def _pshift_rows_cpu(x, w, gE, mask, need_dx, shots, seed, ctr0) -> torch.Tensor:
+    """The kernel's G composed from the host oracles: qsim_probs (fp64) of the shifted weights, then sample_z under
+    the circuit's counter, or the probability-weighted sum in exact mode."""
+    B, n = x.shape
+    P = 2 * n * w.shape[-3]
+    zs = z_signs(n, dtype=torch.float64)
+    g64 = gE.double()
+    G = torch.zeros(B, P, dtype=torch.float32)
+    for p in range(P):
+        if mask is not None and not mask[p] and not (need_dx and p < 2 * n and p % 2 == 0):
+            continue
+        E = []
+        for s, sh in enumerate((0.5 * math.pi, -0.5 * math.pi)):
+            ws = w.clone()
+            ws.view(-1, P)[:, p] += sh
+            pr = qsim_probs(x, ws, "cpu")
+            E.append(sample_z(pr, shots, seed, pshift_counter(ctr0, p, s)).double() if shots else pr @ zs)
+        G[:, p] = (g64 * (E[0] - E[1]) * 0.5).sum(1).float()
+    return G
+
+
+@torch.no_grad()
+def pshift_rows(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, backend: Optional[str] = None,
+                shots: Optional[int] = None, seed: int = 0, counter=0, shift_mask: Optional[torch.Tensor] = None,
+                need_dx: bool = True) -> torch.Tensor:
+    """Per-sample parameter-shift gradients G (B, 2nL) fp32 of sum(gE * qsim(x, w)): column p = (l n + q) 2 + k
+    is w[l, q, k]'s.  dx = G[:, 0:2n:2]; dw = G summed over the samples.  Arguments as for ``qsim``."""
+    _check_shapes(x, w)
+    B, n = x.shape
+    _check_pshift_shape(n, w.shape[-3])
+    shots = _check_shots(shots) if shots else 0
+    be = backend if backend not in (None, "auto") else default_backend(x.device)
+    x = x.detach().float().contiguous()
+    w = w.detach().float().contiguous()
+    gE = gE.detach().float().contiguous()
+    mask = _mask_u8(shift_mask, w)
+    if be == "hip":
+        if x.device.type != "cuda":
+            raise RuntimeError("hip backend needs CUDA/HIP tensors")
+        _hip_shots_limit(n)
+        ctr0, cptr = _split_counter(counter, x.device)
+        G = torch.empty(B, 2 * n * w.shape[-3], device=x.device, dtype=torch.float32)
+        if B > 0:
+            hip_qsim_pshift(x, w, gE, G, None, None, mask, need_dx, shots, int(seed), ctr0, cptr, wgroup_of(x, w))
+        return G
+    if be == "cpu":
+        if x.device.type != "cpu":
+            raise RuntimeError("cpu backend needs CPU tensors")
+        ctr0, _ = _split_counter(counter, x.device)
+        return _pshift_rows_cpu(x, w, gE, mask, need_dx, shots, int(seed), ctr0)
+    if be == "torch":
+        raise ValueError("the torch backend has no parameter-shift rule; use hip or cpu")
+    raise ValueError(f"unknown backend {be!r}")
+
+
+class _QSimPShift(torch.autograd.Function):
+    """Forward: ``qsim``'s own (exact or finite-shot).  Backward: parameter shift with the forward's shots, seed
+    and counter (a device counter is read again by the backward: advance it after the backward)."""
+
+    @staticmethod
+    def forward(ctx, x, w, be, shots, seed, counter, shift_mask):
+        x = x.detach().float().contiguous()
+        w = w.detach().float().contiguous()
+        ctx.save_for_backward(x, w)
+        ctx.args = (be, shots, seed, counter, shift_mask)
+        return qsim(x, w, be, shots=shots, seed=seed, counter=counter)
+
+    @staticmethod
+    def backward(ctx, gE):
+        x, w = ctx.saved_tensors
+        be, shots, seed, counter, shift_mask = ctx.args
+        B, n = x.shape
+        L = w.shape[-3]
+        P = 2 * n * L
+        G = pshift_rows(x, w, gE, be, shots, seed, counter, shift_mask, need_dx=ctx.needs_input_grad[0])
+        dx = G[:, 0:2 * n:2].contiguous()
+        if be == "hip" and B > 0:   # deterministic: no float atomics
+            dw = torch.empty(P, device=x.device, dtype=torch.float32)
+            r = nat.fn(nat.hip_lib(), "qd_reduce_slab", [_p, _p, _i, _i, _f, _p])
+            nat.check(r(nat.ptr(G), nat.ptr(dw), B, P, 0.0, nat.stream_ptr(x.device)), "qd_reduce_slab")
+        else:
+            dw = G.sum(0)
+        if shift_mask is not None:   # (a masked layer-0 RY column still carries dx)
+            dw = dw * _mask_u8(shift_mask, w)
+        dw = dw.view(L, n, 2)
+        if w.dim() == 4:
+            dw = _group_grad(dw, w)
+        return dx, dw, None, None, None, None, None
+
+
 def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots: Optional[int] = None, seed: int = 0,
-         counter=0) -> torch.Tensor:
+         counter=0, diff_method: str = "adjoint", shift_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """<Z_i> of the QSC circuit for inputs x (B, n) and weights w (L, n, 2).
 
     ``w`` may also be grouped, (G, L, n, 2) with B % G == 0: sample b then uses
@@ -437,10 +572,31 @@ def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots:
     on ``cpu``; ``torch`` has no sampler.  The shots of a call are a function of (``seed``, ``counter``, row);
     ``counter`` is an int, or on ``hip`` a CUDA int64 / uint64 scalar tensor the kernel reads (advance it with
     ``counter_add`` after the call: graph replays then draw fresh shots).  The BACKWARD is the exact adjoint of
-    the same (x, w): shot noise is straight-through, the way QuantumNAT's weight noise is treated."""
+    the same (x, w): shot noise is straight-through, the way QuantumNAT's weight noise is treated.
+
+    ``diff_method="parameter_shift"`` (``hip`` with n <= 12, or ``cpu``) keeps that forward and replaces the
+    backward by the parameter-shift rule: every gradient entry comes from two more runs of the circuit with one
+    angle shifted by +-pi/2, each measured with the forward's ``shots`` (None: exactly) -- csrc/hip/qsim_pshift.hip.
+    Shifted circuit (p, s) draws under counter + ((1 + 2p + s) << 48), so its shots never coincide with the
+    forward's or another circuit's for counters below 2^48.  ``shift_mask`` ((L, n, 2) bool, None: all): the
+    parameters whose circuits run; the others get a gradient of exactly 0 (``x``'s gradient is unaffected)."""
     _check_shapes(x, w)
     n = x.shape[1]
     be = backend if backend not in (None, "auto") else default_backend(x.device)
+    if diff_method not in DIFF_METHODS:
+        raise ValueError(f"unknown diff_method {diff_method!r}: one of {DIFF_METHODS}")
+    if diff_method == "parameter_shift":
+        if be == "torch":
+            raise ValueError("the torch backend has no parameter-shift rule; use hip or cpu")
+        if be not in ("hip", "cpu"):
+            raise ValueError(f"unknown backend {be!r}")
+        if be == "hip" and x.device.type == "cuda":
+            _hip_shots_limit(n)
+        _check_pshift_shape(n, w.shape[-3])
+        _mask_u8(shift_mask, w)
+        return _QSimPShift.apply(x, w, be, _check_shots(shots) if shots else None, int(seed), counter, shift_mask)
+    if shift_mask is not None:
+        raise ValueError("shift_mask needs diff_method='parameter_shift'")
     if shots:
         shots = _check_shots(shots)
         if be == "torch":
