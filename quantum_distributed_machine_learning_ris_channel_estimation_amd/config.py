@@ -117,6 +117,14 @@ class EvalConfig:
     hdce_tag: str = ""
     # measurement shots per sample of the quantum SC's circuit (0: exact expectation values; ops/quantum.py qsim)
     qsc_shots: int = 0
+    # the device noise those shots are measured under (used only with qsc_shots > 0; ops/quantum.py NoiseModel):
+    # Pauli error rate per fused one-qubit gate / per CNOT, readout error 0 -> 1 / 1 -> 0, and the number of gate-
+    # error realisations the shots are split over
+    qsc_noise_p1: float = 0.0
+    qsc_noise_p2: float = 0.0
+    qsc_readout01: float = 0.0
+    qsc_readout10: float = 0.0
+    qsc_trajectories: int = 1
 
     def update_from_dict(self, d: Dict[str, Any]) -> "EvalConfig":
         names = {f.name for f in dataclasses.fields(self)}

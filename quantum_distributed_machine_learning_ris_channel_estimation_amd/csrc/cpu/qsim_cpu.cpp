@@ -218,3 +218,165 @@ QD_API int qd_cpu_sample_z(const float* probs, float* E, int32_t* counts, int B,
   }
   return 0;
 }
+
+// ------------------------------------------------------------------------------- Pauli noise (csrc/hip/qsim_noise.hip)
+// The noise contract of csrc/hip/qsim_noise.hip (see its header), sequentially.
+namespace {
+inline uint32_t pauli_x(uint32_t p) { return ((p + 1u) >> 1) & 1u; }   // 0 .. 3 = I, X, Y, Z
+inline uint32_t pauli_z(uint32_t p) { return (p >> 1) & 1u; }
+inline bool noise_shape_ok(int n, int L) { return n >= 2 && n <= 12 && L >= 1 && 2 * n * L <= 4096; }
+inline bool traj_ok(int shots, int T) {
+  if (shots < 1 || shots > (1 << 20) || T < 1 || T > 1024 || shots % T != 0) return false;
+  return T == 1 || (shots / T) % 4 == 0;
+}
+}  // namespace
+
+// sites (B, T, L, n, 2) uint8: the error code drawn at every site (0: none; k = 0: 1 .. 3, k = 1: 1 .. 15).
+// thr1 / thr2 (n) uint32 thresholds.
+QD_API int qd_cpu_noise_sites(uint8_t* sites, const uint32_t* thr1, const uint32_t* thr2, int B, int n, int L, int T,
+                              uint64_t seed, uint64_t ctr) {
+  if (!noise_shape_ok(n, L) || B < 0 || T < 1 || T > 1024) return 1;
+  const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+  const int nsites = 2 * n * L;
+#pragma omp parallel for schedule(static)
+  for (int b = 0; b < B; ++b) {
+    for (int tau = 0; tau < T; ++tau) {
+      uint8_t* out = sites + ((size_t)b * T + tau) * nsites;
+      uint32_t rnd[4] = {0, 0, 0, 0};
+      for (int s = 0; s < nsites; ++s) {
+        if ((s & 3) == 0) {
+          const uint32_t c4[4] = {0x80000000u | ((uint32_t)tau << 10) | ((uint32_t)s >> 2), (uint32_t)b, (uint32_t)ctr,
+                                  (uint32_t)(ctr >> 32)};
+          qd_cpu_philox4x32(c4, key, rnd);
+        }
+        const int q = (s >> 1) % n, k = s & 1;
+        const uint32_t r = rnd[s & 3], thr = k ? thr2[q] : thr1[q];
+        out[s] = r < thr ? (uint8_t)(1u + (uint32_t)(((uint64_t)r * (k ? 15u : 3u)) / thr)) : (uint8_t)0;
+      }
+    }
+  }
+  return 0;
+}
+
+// frames (rows, L, 2) int32 = every layer's (a, b) from the site codes (rows, L, n, 2) uint8.
+QD_API int qd_cpu_pauli_frames(const uint8_t* sites, int32_t* frames, int rows, int n, int L) {
+  if (!noise_shape_ok(n, L) || rows < 0) return 1;
+  for (size_t i = 0; i < (size_t)rows * L * n; ++i)
+    if (sites[2 * i] > 3 || sites[2 * i + 1] > 15) return 1;
+#pragma omp parallel for schedule(static)
+  for (int r = 0; r < rows; ++r) {
+    for (int l = 0; l < L; ++l) {
+      const uint8_t* c = sites + ((size_t)r * L + l) * n * 2;
+      uint32_t a = 0, z = 0;
+      for (int q = 0; q < n; ++q) {
+        a |= pauli_x(c[2 * q]) << q;
+        z |= pauli_z(c[2 * q]) << q;
+      }
+      for (int q = 0; q < n; ++q) {
+        const int t = (q + 1) % n;
+        a ^= ((a >> q) & 1u) << t;
+        z ^= ((z >> t) & 1u) << q;
+        const uint32_t pc = c[2 * q + 1] >> 2, pt = c[2 * q + 1] & 3u;
+        a ^= (pauli_x(pc) << q) ^ (pauli_x(pt) << t);
+        z ^= (pauli_z(pc) << q) ^ (pauli_z(pt) << t);
+      }
+      frames[((size_t)r * L + l) * 2] = (int32_t)a;
+      frames[((size_t)r * L + l) * 2 + 1] = (int32_t)z;
+    }
+  }
+  return 0;
+}
+
+// probs (B, 2^n) double of the circuit with row b's frames (B, L, 2) int32 applied behind the rings of layers
+// 0 .. L-2: A'[j] = (-1)^popc(b & (j ^ a)) A[j ^ a].  The last layer's frame is left out (it acts on the outcome).
+QD_API int qd_cpu_qsim_probs_framed(const float* x, const float* w, const int32_t* frames, double* probs, int B, int n,
+                                    int L) {
+  if (!noise_shape_ok(n, L) || B < 0) return 1;
+  const size_t D = size_t(1) << n;
+  for (size_t i = 0; i < (size_t)B * L * 2; ++i)
+    if (frames[i] < 0 || (size_t)frames[i] >= D) return 1;
+  const int per = 3 * n;   // gates of a layer
+#pragma omp parallel for schedule(static)
+  for (int b = 0; b < B; ++b) {
+    const auto gates = build_circuit(x + (size_t)b * n, w, n, L);
+    std::vector<cd> s(D, cd(0)), t(D);
+    s[0] = 1.0;
+    size_t gi = 0;
+    for (; gi < (size_t)n; ++gi) apply(s, gates[gi], false);   // the embedding
+    for (int l = 0; l < L; ++l) {
+      for (int k = 0; k < per; ++k, ++gi) apply(s, gates[gi], false);
+      if (l == L - 1) break;
+      const size_t fa = (size_t)frames[((size_t)b * L + l) * 2], fb = (size_t)frames[((size_t)b * L + l) * 2 + 1];
+      if (fa == 0 && fb == 0) continue;
+      for (size_t j = 0; j < D; ++j) {
+        const size_t js = j ^ fa;
+        t[j] = (__builtin_popcountll(fb & js) & 1) ? -s[js] : s[js];
+      }
+      s.swap(t);
+    }
+    for (size_t k = 0; k < D; ++k) probs[(size_t)b * D + k] = std::norm(s[k]);
+  }
+  return 0;
+}
+
+// Noisy finite-shot <Z_i>: probs (B, T, 2^n) fp32, one distribution per trajectory; amask (B, T) int32, the last
+// layer's X masks; thr_ro (n, 2) uint32 readout thresholds ([i][0]: reads 1 given 0, [i][1]: reads 0 given 1).
+QD_API int qd_cpu_sample_z_noisy(const float* probs, const int32_t* amask, const uint32_t* thr_ro, float* E,
+                                 int32_t* counts, int B, int n, int shots, int T, uint64_t seed, uint64_t ctr) {
+  if (n < 2 || n > 12 || !traj_ok(shots, T) || B < 0) return 1;
+  const size_t D = size_t(1) << n;
+  for (size_t i = 0; i < (size_t)B * T; ++i)
+    if (amask[i] < 0 || (size_t)amask[i] >= D) return 1;
+  bool readout = false;
+  for (int i = 0; i < 2 * n; ++i) {
+    if (thr_ro[i] > 65535u) return 1;
+    readout |= thr_ro[i] != 0;
+  }
+  const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+  const int S = shots / T;
+#pragma omp parallel for schedule(static)
+  for (int b = 0; b < B; ++b) {
+    std::vector<uint32_t> cum(D);
+    std::vector<int32_t> c1(n, 0);
+    uint32_t rnd[4] = {0, 0, 0, 0}, ro[4] = {0, 0, 0, 0};
+    uint32_t T_cdf = 0;
+    for (int s = 0; s < shots; ++s) {
+      const int tau = s / S;
+      if (s % S == 0) {   // the trajectory's CDF
+        uint32_t run = 0;
+        const float* p = probs + ((size_t)b * T + tau) * D;
+        for (size_t k = 0; k < D; ++k) {
+          run += p[k] > 0.f ? (uint32_t)std::nearbyintf(p[k] * 1073741824.f) : 0u;
+          cum[k] = run;
+        }
+        T_cdf = run;
+      }
+      if ((s & 3) == 0) {
+        const uint32_t c4[4] = {(uint32_t)s >> 2, (uint32_t)b, (uint32_t)ctr, (uint32_t)(ctr >> 32)};
+        qd_cpu_philox4x32(c4, key, rnd);
+      }
+      const uint32_t t = (uint32_t)(((uint64_t)rnd[s & 3] * T_cdf) >> 32);
+      size_t k = std::upper_bound(cum.begin(), cum.end(), t) - cum.begin();
+      if (k > D - 1) k = D - 1;
+      k ^= (size_t)amask[(size_t)b * T + tau];
+      if (readout) {
+        for (int i = 0; i < n; ++i) {
+          if ((i & 7) == 0) {
+            const uint32_t c4[4] = {0x40000000u | ((uint32_t)s << 1) | ((uint32_t)i >> 3), (uint32_t)b, (uint32_t)ctr,
+                                    (uint32_t)(ctr >> 32)};
+            qd_cpu_philox4x32(c4, key, ro);
+          }
+          const uint32_t field = (ro[(i & 7) >> 1] >> (16 * (i & 1))) & 0xFFFFu;
+          const uint32_t bit = (uint32_t)(k >> i) & 1u;
+          if (field < thr_ro[2 * i + bit]) k ^= size_t(1) << i;
+        }
+      }
+      for (int i = 0; i < n; ++i) c1[i] += (int32_t)((k >> i) & 1);
+    }
+    for (int i = 0; i < n; ++i) {
+      E[(size_t)b * n + i] = (float)(shots - 2 * c1[i]) / (float)shots;
+      if (counts != nullptr) counts[(size_t)b * n + i] = c1[i];
+    }
+  }
+  return 0;
+}

@@ -1,6 +1,6 @@
-// Device functions of the finite-shot kernels (qsim_shots.hip, qsim_pshift.hip): the LDS-resident state build of the
-// QSC circuit, the CDF scan, Philox4x32-10 and the outcome search.  The sampling contract they implement is stated
-// at the top of qsim_shots.hip.
+// Device functions of the finite-shot kernels (qsim_shots.hip, qsim_pshift.hip, qsim_noise.hip): the LDS-resident
+// state build of the QSC circuit (FRAMED: with a Pauli frame behind a layer's ring, for qsim_noise.hip), the CDF scan,
+// Philox4x32-10 and the outcome search.  The sampling contract they implement is stated at the top of qsim_shots.hip.
 #pragma once
 #include "common.h"
 
@@ -60,28 +60,36 @@ __device__ __forceinline__ void gate_fwd(cf& a0, cf& a1, float4 t) {
   a1 = cmul(t1, cf{t.z, t.w});
 }
 
+// Sign of a Pauli frame's Z mask fb on basis state js: -a when popc(fb & js) is odd.
+__device__ __forceinline__ cf frame_sign(cf a, int fb, int js) {
+  return (__popc(fb & js) & 1) ? cf{-a.x, -a.y} : a;
+}
+
 // Embedding + layer 0 + ring from the layer's trig: the product state gathered through f^-1, into A (LDS).
-template <int N>
-__device__ __forceinline__ void product_state(cf* A, const float4* trig) {
+// FRAMED (qsim_noise.hip): followed by the Pauli frame X^fa Z^fb, A'[j] = (-1)^popc(fb & (j ^ fa)) A[j ^ fa].
+template <int N, bool FRAMED = false>
+__device__ __forceinline__ void product_state(cf* A, const float4* trig, int fa = 0, int fb = 0) {
   constexpr int D = 1 << N;
   for (int j = threadIdx.x; j < D; j += NT) {
-    const int k = ring_inv<N>(j);
+    const int js = FRAMED ? (j ^ fa) : j;
+    const int k = ring_inv<N>(js);
     cf a = {1.f, 0.f};
 #pragma unroll
     for (int q = 0; q < N; ++q) {
       const float4 t = trig[q];
       a = cmul(a, ((k >> q) & 1) ? cf{t.y * t.z, t.y * t.w} : cf{t.x * t.z, -t.x * t.w});
     }
-    A[j] = a;
+    A[j] = FRAMED ? frame_sign(a, fb, js) : a;
   }
   __syncthreads();
 }
 
 // One layer (its trig in LDS, visible) applied to the state in S, the result in A (S == A: in place; else S is
 // left as it was).  Ends with a barrier.  GB: qubits per LDS round trip; FIRST: the first group of qubits to sweep
-// (1: the caller has applied group 0's gates on its way into A).
-template <int N, int GB = 3, int FIRST = 0>
-__device__ __forceinline__ void apply_layer(const cf* S, cf* A, const float4* trig) {
+// (1: the caller has applied group 0's gates on its way into A).  FRAMED: the Pauli frame (fa, fb) after the ring,
+// folded into the ring gather's index and sign.
+template <int N, int GB = 3, int FIRST = 0, bool FRAMED = false>
+__device__ __forceinline__ void apply_layer(const cf* S, cf* A, const float4* trig, int fa = 0, int fb = 0) {
   constexpr int D = 1 << N;
   constexpr int PER = D >= NT ? D / NT : 1;   // amplitudes per thread of the ring pass
   // pair sweeps, up to GB qubits per LDS round trip: a thread owns the 2^NB amplitudes that differ in the
@@ -112,7 +120,11 @@ __device__ __forceinline__ void apply_layer(const cf* S, cf* A, const float4* tr
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int j = threadIdx.x + i * NT;
-    if (j < D) a[i] = A[ring_inv<N>(j)];
+    if (FRAMED) {
+      if (j < D) a[i] = frame_sign(A[ring_inv<N>(j ^ fa)], fb, j ^ fa);
+    } else {
+      if (j < D) a[i] = A[ring_inv<N>(j)];
+    }
   }
   __syncthreads();
 #pragma unroll

@@ -88,16 +88,22 @@ class QuantumLayer(nn.Module):
     ``diff_method`` (settable; "adjoint" or "parameter_shift") selects the backward: the exact adjoint, or the
     parameter-shift rule measured with the same ``shots`` (``qsim(diff_method=)``).  ``shift_mask`` (settable;
     None or a (n_layers, n_qubits, 2) bool tensor) names the parameters whose shifted circuits run; the others
-    get a zero gradient.  Both are plain attributes too."""
+    get a zero gradient.  Both are plain attributes too.
+
+    ``noise`` (settable; None or an ``ops.quantum.NoiseModel``) and ``trajectories`` (settable; 1 .. 1024) measure
+    the shots on a device with Pauli gate errors and readout error (``qsim(noise=, trajectories=)``); they need
+    ``shots``, and gradients stay those of the noiseless circuit."""
 
     def __init__(self, n_qubits: int, n_layers: int, backend: Optional[str] = None, shots: Optional[int] = None,
-                 diff_method: str = "adjoint"):
+                 diff_method: str = "adjoint", noise=None, trajectories: int = 1):
         super().__init__()
         self.n_qubits, self.n_layers = n_qubits, n_layers
         self.backend = backend
         self.shots = shots
         self.diff_method = diff_method
         self.shift_mask = None
+        self.noise = noise
+        self.trajectories = trajectories
         self.shot_seed = 0
         self._shot_calls = 0
         self.weights = nn.Parameter(init_weights_(torch.empty(n_layers, n_qubits, 2)))
@@ -110,6 +116,8 @@ class QuantumLayer(nn.Module):
     def forward(self, x: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         w = self.weights if weights is None else weights
         kw = {} if self.diff_method == "adjoint" else {"diff_method": self.diff_method, "shift_mask": self.shift_mask}
+        if self.noise is not None:
+            kw.update(noise=self.noise, trajectories=int(self.trajectories))
         if not self.shots:
             return qsim(x.float(), w, self.backend, **kw)
         call = self._shot_calls
@@ -137,13 +145,14 @@ class QSC_P128(nn.Module):
     defined there): Linear(n, n) + Tanh in place of the VQC, an equal-width classical ablation
     with the same (-1, 1) output range as <Z_i>.
     ``shots`` goes to the ``qlayer`` (finite-shot <Z_i>; None = exact), and so does ``diff_method``
-    ("adjoint", or "parameter_shift": the gradient an on-chip QNN measures).
+    ("adjoint", or "parameter_shift": the gradient an on-chip QNN measures), ``noise`` and ``trajectories``
+    (the device's gate and readout errors under which the shots are measured).
     """
 
     def __init__(self, n_qubits: int = 6, n_layers: int = 3, n_classes: int = 3, use_quantumnat: bool = True,
                  use_gradient_pruning: bool = True, pilot_num: int = 128, backend: Optional[str] = None,
                  noise_level: float = 0.01, gradient_threshold: float = 0.1, use_quantum: bool = True,
-                 shots: Optional[int] = None, diff_method: str = "adjoint"):
+                 shots: Optional[int] = None, diff_method: str = "adjoint", noise=None, trajectories: int = 1):
         super().__init__()
         self.use_quantum = use_quantum
         self.num_qubits = n_qubits
@@ -157,7 +166,7 @@ class QSC_P128(nn.Module):
         H, W = pilot_grid(pilot_num)
         flat = 32 * (H // 4) * (W // 4)
         # registration order matters: qlayer.weights is the first state_dict key (E:149 < E:152)
-        self.qlayer = QuantumLayer(n_qubits, n_layers, backend, shots, diff_method)
+        self.qlayer = QuantumLayer(n_qubits, n_layers, backend, shots, diff_method, noise, trajectories)
         self.preprocess = nn.Sequential(
             nn.Conv2d(2, 16, kernel_size=3, stride=1, padding=1),
             nn.ReLU(),

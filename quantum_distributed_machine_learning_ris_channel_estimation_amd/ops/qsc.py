@@ -285,23 +285,33 @@ class QSCStepHIP:
 
     @torch.no_grad()
     def infer(self, x: torch.Tensor, pred: Optional[torch.Tensor] = None,
-              logp: Optional[torch.Tensor] = None, shots: int = 0, seed: int = 0, counter=0) -> None:
+              logp: Optional[torch.Tensor] = None, shots: int = 0, seed: int = 0, counter=0, noise=None,
+              trajectories: int = 1) -> None:
         """Inference on the HIP kernels (x.shape[0] == B): preprocess CNN, the circuit with the clean
         master weights (no QuantumNAT noise), then a thread-per-sample head -> log-probabilities (B, C)
         and / or the argmax (B,) int64.  ``shots`` > 0: the circuit's <Z_i> are finite-shot estimates
         (csrc/hip/qsim_shots.hip's fused kernel on the angles, n <= 12; ``seed`` / ``counter`` as in
-        ops.quantum.qsim)."""
+        ops.quantum.qsim).  ``noise`` / ``trajectories`` (with ``shots``): the shots are measured under that
+        ``NoiseModel`` (csrc/hip/qsim_noise.hip)."""
         m = self.m
         B, n, L = self.B, self.n, self.L
         assert x.shape[0] == B and x.is_contiguous() and self.impl == "mfma"
         st = nat.stream_ptr(x.device)
         self._fwd_mfma(x, self.space.flat, st)
         w = m.qlayer.weights.detach().contiguous()
+        if noise is not None and not shots:
+            raise ValueError("noise needs shots")
         if shots:
             from . import quantum as Q
             Q._hip_shots_limit(n)
             ctr0, cptr = Q._split_counter(counter, x.device)
-            Q.hip_qsim_shots_fwd(self.angles, w, self.E, None, Q._check_shots(shots), int(seed), ctr0, cptr)
+            shots = Q._check_shots(shots)
+            if noise is not None:
+                Q._check_noise_shape(n, L)
+                Q.hip_qsim_noisy_shots_fwd(self.angles, w, self.E, None, noise, shots,
+                                           Q._check_trajectories(shots, trajectories), int(seed), ctr0, cptr)
+            else:
+                Q.hip_qsim_shots_fwd(self.angles, w, self.E, None, shots, int(seed), ctr0, cptr)
         else:
             extra = (nat.ptr(self.qws) if self.qws is not None else None,
                      nat.ptr(self.psave) if self.psave is not None else None) if self.big else \

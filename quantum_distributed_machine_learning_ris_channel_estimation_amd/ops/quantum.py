@@ -24,6 +24,11 @@ measurement shots of the final state -- csrc/hip/qsim_shots.hip (n <= 12) on ``h
 Parameter shift (``qsim(..., diff_method="parameter_shift")``, ``pshift_rows``): the backward an on-chip QNN can
 measure -- two more runs of the circuit per parameter, one angle shifted by +-pi/2, exact or with the forward's
 finite shots; csrc/hip/qsim_pshift.hip (n <= 12) on ``hip``, composed from ``qsim_probs`` and ``sample_z`` on ``cpu``.
+
+Device noise (``NoiseModel``, ``qsim(..., shots=N, noise=, trajectories=T)``, ``noise_sites``, ``pauli_frames``,
+``qsim_probs(frames=)``, ``sample_z_noisy``): the shots are measured under Pauli gate errors and readout error, the
+gate errors of each of T trajectories collapsed into one Pauli frame per layer -- csrc/hip/qsim_noise.hip (n <= 12)
+on ``hip``, composed from the C++ oracles of the same integer contract on ``cpu``; gradients stay straight-through.
 """
 from __future__ import annotations
 
@@ -322,12 +327,19 @@ def _hip_shots_limit(n: int) -> None:
 
 
 @torch.no_grad()
-def qsim_probs(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None) -> torch.Tensor:
+def qsim_probs(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None,
+               frames: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Outcome probabilities |amp_k|^2 of the QSC circuit, (B, 2^n) in natural basis order (the ``qml.probs``
-    counterpart): fp32 on ``hip`` (n <= 12), fp64 on ``cpu``, the eager simulator's on ``torch``.  No autograd."""
+    counterpart): fp32 on ``hip`` (n <= 12), fp64 on ``cpu``, the eager simulator's on ``torch``.  No autograd.
+
+    ``frames`` ((B, L, 2) int32, ``cpu`` only: the oracle of csrc/hip/qsim_noise.hip): row b's Pauli frames
+    (a, b), applied behind the rings of layers 0 .. L-2; the last layer's frame acts on the outcome and is
+    left out."""
     _check_shapes(x, w)
     B, n = x.shape
     be = backend if backend not in (None, "auto") else default_backend(x.device)
+    if frames is not None:
+        return _qsim_probs_framed(x, w, be, frames)
     if be == "hip":
         if x.device.type != "cuda":
             raise RuntimeError("hip backend needs CUDA/HIP tensors")
@@ -427,6 +439,253 @@ class _ReplaceValue(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return g, None
+
+
+# ----------------------------------------------------------------------------- Pauli noise
+MAX_TRAJECTORIES = 1024
+MAX_NOISE_SITES = 4096   # 2 n L
+
+
+class NoiseModel:
+    """Gate and readout noise of a device, for ``qsim(shots=, noise=)`` (csrc/hip/qsim_noise.hip).
+
+    Every argument is a float or a length-n sequence, a probability in [0, 0.5]:
+    ``p1[q]``: a uniformly drawn X / Y / Z after wire q's fused RZ.RY of every layer;
+    ``p2[q]``: a uniformly drawn non-identity two-qubit Pauli after every CNOT whose control is wire q;
+    ``readout01[i]`` / ``readout10[i]``: wire i reads 1 given 0 / 0 given 1.
+
+    The kernels compare integers: ``thresholds(n, device)`` gives thr = min(rint(p 2^32), 2^32 - 1) for the gates
+    (uint32 bits in int32 tensors) and thr16 = min(rint(r 2^16), 65535) for the readout ((n, 2) int32), computed
+    in float64 on the host and cached per (n, device)."""
+
+    FIELDS = ("p1", "p2", "readout01", "readout10")
+
+    def __init__(self, p1=0.0, p2=0.0, readout01=0.0, readout10=0.0):
+        import numpy as np
+        for name, v in zip(self.FIELDS, (p1, p2, readout01, readout10)):
+            a = np.atleast_1d(np.asarray(v, dtype=np.float64))
+            if a.ndim != 1 or a.size < 1 or not np.all((a >= 0.0) & (a <= 0.5)):   # (NaN fails too)
+                raise ValueError(f"{name} must be a probability in [0, 0.5] or a sequence of them, got {v!r}")
+            setattr(self, name, a if a.size > 1 else float(a[0]))
+        self._cache = {}
+
+    def _per_wire(self, name: str, n: int):
+        import numpy as np
+        v = getattr(self, name)
+        if isinstance(v, float):
+            return np.full(n, v, dtype=np.float64)
+        if v.size != n:
+            raise ValueError(f"{name} has {v.size} entries for {n} wires")
+        return v
+
+    @property
+    def is_zero(self) -> bool:
+        import numpy as np
+        return all(not np.any(np.asarray(getattr(self, f))) for f in self.FIELDS)
+
+    def thresholds_host(self, n: int):
+        """(thr1 (n) uint32, thr2 (n) uint32, thr_ro (n, 2) uint32) as NumPy arrays."""
+        import numpy as np
+        gate = lambda p: np.minimum(np.rint(p * 4294967296.0), 4294967295.0).astype(np.uint32)   # noqa: E731
+        ro = lambda r: np.minimum(np.rint(r * 65536.0), 65535.0).astype(np.uint32)   # noqa: E731
+        thr_ro = np.stack([ro(self._per_wire("readout01", n)), ro(self._per_wire("readout10", n))], axis=1)
+        return gate(self._per_wire("p1", n)), gate(self._per_wire("p2", n)), np.ascontiguousarray(thr_ro)
+
+    def thresholds(self, n: int, device) -> tuple:
+        device = torch.device(device)
+        key = (n, device.type, device.index)
+        if key not in self._cache:
+            self._cache[key] = tuple(torch.from_numpy(t.view("int32").copy()).to(device)
+                                     for t in self.thresholds_host(n))
+        return self._cache[key]
+
+    def __repr__(self) -> str:
+        return "NoiseModel(" + ", ".join(f"{f}={getattr(self, f)!r}" for f in self.FIELDS) + ")"
+
+
+def _check_trajectories(shots: int, T) -> int:
+    T = int(T)
+    if not 1 <= T <= MAX_TRAJECTORIES:
+        raise ValueError(f"trajectories must be in 1..{MAX_TRAJECTORIES}, got {T}")
+    if shots % T:
+        raise ValueError(f"shots ({shots}) must be a multiple of trajectories ({T})")
+    if T > 1 and (shots // T) % 4:
+        raise ValueError(f"with trajectories > 1, shots / trajectories must be a multiple of 4, got {shots // T}")
+    return T
+
+
+def _check_noise_shape(n: int, L: int) -> None:
+    if 2 * n * L > MAX_NOISE_SITES:
+        raise ValueError(f"the noise model supports 2 n L <= {MAX_NOISE_SITES} error sites, got n={n} L={L}")
+
+
+@torch.no_grad()
+def noise_sites(noise: NoiseModel, B: int, n: int, L: int, T: int = 1, seed: int = 0, counter: int = 0,
+                device=None) -> torch.Tensor:
+    """The error code drawn at every site of every trajectory, (B, T, L, n, 2) uint8: [..., q, 0] after wire q's
+    RZ.RY (0 none, 1 / 2 / 3 = X / Y / Z), [..., q, 1] after CNOT(q, q+1) (0 none, else 4 P_control + P_target).
+    Drawn on the host by the C++ oracle of the kernel's contract."""
+    _check_noise_shape(n, L)
+    if not 1 <= int(T) <= MAX_TRAJECTORIES:
+        raise ValueError(f"trajectories must be in 1..{MAX_TRAJECTORIES}, got {T}")
+    if n > HIP_SHOTS_MAX_QUBITS:
+        raise NotImplementedError(f"the noise model supports n <= {HIP_SHOTS_MAX_QUBITS} qubits, got {n}")
+    thr1, thr2, _ = noise.thresholds(n, "cpu")
+    sites = torch.zeros(B, T, L, n, 2, dtype=torch.uint8)
+    f = nat.fn(nat.cpu_lib(), "qd_cpu_noise_sites", [_p, _p, _p, _i, _i, _i, _i, _u64, _u64])
+    nat.check(f(nat.ptr(sites), nat.ptr(thr1), nat.ptr(thr2), B, n, L, int(T), int(seed) & _M64, int(counter) & _M64),
+              "qd_cpu_noise_sites")
+    return sites.to(device) if device is not None else sites
+
+
+@torch.no_grad()
+def pauli_frames(sites: torch.Tensor) -> torch.Tensor:
+    """Site codes (..., L, n, 2) uint8 -> every layer's Pauli frame (..., L, 2) int32 = (X mask a, Z mask b)
+    behind that layer's CNOT ring."""
+    if sites.dim() < 3 or sites.shape[-1] != 2 or sites.dtype != torch.uint8:
+        raise ValueError(f"sites must be (..., L, n, 2) uint8, got {tuple(sites.shape)} {sites.dtype}")
+    L, n = sites.shape[-3], sites.shape[-2]
+    _check_noise_shape(n, L)
+    host = sites.detach().cpu().contiguous()
+    rows = host.numel() // (2 * n * L)
+    frames = torch.zeros(*sites.shape[:-3], L, 2, dtype=torch.int32)
+    f = nat.fn(nat.cpu_lib(), "qd_cpu_pauli_frames", [_p, _p, _i, _i, _i])
+    nat.check(f(nat.ptr(host), nat.ptr(frames), rows, n, L), "qd_cpu_pauli_frames")
+    return frames.to(sites.device)
+
+
+def _qsim_probs_framed(x: torch.Tensor, w: torch.Tensor, be: str, frames: torch.Tensor) -> torch.Tensor:
+    B, n = x.shape
+    L = w.shape[-3]
+    if be != "cpu":
+        raise ValueError("qsim_probs(frames=) is the host oracle: backend 'cpu' only")
+    if x.device.type != "cpu":
+        raise RuntimeError("cpu backend needs CPU tensors")
+    if tuple(frames.shape) != (B, L, 2) or frames.dtype != torch.int32:
+        raise ValueError(f"frames must be ({B}, {L}, 2) int32, got {tuple(frames.shape)} {frames.dtype}")
+    _check_noise_shape(n, L)
+    if w.dim() == 4:
+        G = w.shape[0]
+        return torch.cat([_qsim_probs_framed(xc, w[g], be, fc) for g, (xc, fc) in
+                          enumerate(zip(x.chunk(G), frames.chunk(G)))], dim=0)
+    x = x.detach().float().contiguous()
+    w = w.detach().float().contiguous()
+    frames = frames.detach().cpu().contiguous()
+    probs = torch.empty(B, 1 << n, dtype=torch.float64)
+    f = nat.fn(nat.cpu_lib(), "qd_cpu_qsim_probs_framed", [_p, _p, _p, _p, _i, _i, _i])
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(frames), nat.ptr(probs), B, n, L), "qd_cpu_qsim_probs_framed")
+    return probs
+
+
+@torch.no_grad()
+def sample_z_noisy(probs: torch.Tensor, amask: torch.Tensor, noise: NoiseModel, shots: int, seed: int = 0,
+                   counter: int = 0, return_counts: bool = False):
+    """The host oracle of the noisy sampler: probs (B, T, 2^n) (cast to fp32), one distribution per trajectory;
+    amask (B, T) int32, the X mask of each trajectory's last-layer frame; readout error from ``noise``.
+    Trajectory tau owns shots [tau shots/T, (tau+1) shots/T).  E (B, n) fp32 (and counts (B, n) int32)."""
+    shots = _check_shots(shots)
+    if probs.dim() != 3 or probs.shape[2] < 4 or probs.shape[2] & (probs.shape[2] - 1):
+        raise ValueError(f"probs must be (B, T, 2^n) with n >= 2, got {tuple(probs.shape)}")
+    B, T, n = probs.shape[0], probs.shape[1], probs.shape[2].bit_length() - 1
+    _check_trajectories(shots, T)
+    if n > HIP_SHOTS_MAX_QUBITS:
+        raise NotImplementedError(f"the shot samplers support n <= {HIP_SHOTS_MAX_QUBITS} qubits, got {n}")
+    if tuple(amask.shape) != (B, T):
+        raise ValueError(f"amask must be ({B}, {T}), got {tuple(amask.shape)}")
+    probs = probs.detach().cpu().float().contiguous()
+    amask = amask.detach().cpu().to(torch.int32).contiguous()
+    thr_ro = noise.thresholds(n, "cpu")[2]
+    E = torch.empty(B, n, dtype=torch.float32)
+    counts = torch.empty(B, n, dtype=torch.int32)
+    f = nat.fn(nat.cpu_lib(), "qd_cpu_sample_z_noisy", [_p, _p, _p, _p, _p, _i, _i, _i, _i, _u64, _u64])
+    nat.check(f(nat.ptr(probs), nat.ptr(amask), nat.ptr(thr_ro), nat.ptr(E), nat.ptr(counts), B, n, shots, T,
+                int(seed) & _M64, int(counter) & _M64), "qd_cpu_sample_z_noisy")
+    return (E, counts) if return_counts else E
+
+
+def hip_qsim_noisy_shots_fwd(x: torch.Tensor, w: torch.Tensor, E: torch.Tensor, counts: Optional[torch.Tensor],
+                             noise: NoiseModel, shots: int, trajectories: int = 1, seed: int = 0, ctr0: int = 0,
+                             counter_ptr=None, wgroup: int = 0, probs_out: Optional[torch.Tensor] = None,
+                             frames_out: Optional[torch.Tensor] = None) -> None:
+    """Raw launcher of csrc/hip/qsim_noise.hip (n <= 12): E (B, n) fp32 / counts (B, n) int32 (nullable) of
+    ``shots`` noisy shots per sample over ``trajectories`` error realisations; probs_out (nullable; B, T, 2^n)
+    fp32 the probabilities each trajectory's CDF was quantised from, frames_out (nullable; B, T, L, 2) int32."""
+    B, n = x.shape
+    thr1, thr2, thr_ro = noise.thresholds(n, x.device)
+    f = nat.fn(nat.hip_lib(), "qd_qsim_noisy_shots_fwd",
+               [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _u64, _u64, _p, _p])
+    opt = lambda t: nat.ptr(t) if t is not None else None   # noqa: E731
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(E), opt(counts), opt(probs_out), opt(frames_out), nat.ptr(thr1),
+                nat.ptr(thr2), nat.ptr(thr_ro), B, n, w.shape[-3], wgroup, shots, int(trajectories), seed & _M64,
+                ctr0 & _M64, counter_ptr, nat.stream_ptr(x.device)), "qd_qsim_noisy_shots_fwd")
+
+
+def noise_split(trajectories: int, n: int) -> int:
+    """The workgroups per sample the noisy kernel launches for that many trajectories of n qubits (1: one per sample; else one
+    per (sample, chunk of trajectories), the counts meeting through integer atomics: the result does not depend
+    on it)."""
+    return nat.fn(nat.hip_lib(), "qd_qsim_noise_split", [_i, _i])(int(trajectories), int(n))
+
+
+def noise_force_split(nsplit: int) -> None:
+    """Tests and timing: launch ``nsplit`` (1, 2, 4 or 8; it must divide ``trajectories``) workgroups per sample
+    from now on; 0 hands the choice back to the launcher."""
+    nat.check(nat.fn(nat.hip_lib(), "qd_qsim_noise_force_split", [_i])(int(nsplit)), "qd_qsim_noise_force_split")
+
+
+@torch.no_grad()
+def _noisy_shots_cpu(x, w, noise, shots, T, seed, ctr0) -> torch.Tensor:
+    """The noisy forward composed from the host oracles: sites -> frames -> framed probabilities -> sampler."""
+    B, n = x.shape
+    L = w.shape[-3]
+    frames = pauli_frames(noise_sites(noise, B, n, L, T, seed, ctr0))
+    probs = qsim_probs(x.repeat_interleave(T, dim=0), w, "cpu", frames=frames.view(B * T, L, 2))
+    return sample_z_noisy(probs.view(B, T, 1 << n), frames[:, :, L - 1, 0], noise, shots, seed, ctr0)
+
+
+class _QSimNoisyHIP(torch.autograd.Function):
+    """Forward: the noisy finite-shot kernel.  Backward: the exact adjoint of the noiseless circuit (gate, readout
+    and shot noise are straight-through)."""
+
+    @staticmethod
+    def forward(ctx, x, w, wgroup, noise, shots, T, seed, ctr0, cptr):
+        B, n = x.shape
+        x = x.detach().float().contiguous()
+        w = w.detach().float().contiguous()
+        E = torch.empty(B, n, device=x.device, dtype=torch.float32)
+        if B > 0:
+            hip_qsim_noisy_shots_fwd(x, w, E, None, noise, shots, T, seed, ctr0, cptr, wgroup)
+        ctx.save_for_backward(x, w)
+        return E
+
+    @staticmethod
+    def backward(ctx, gE):
+        dx, dw, _ = _QSimHIP.backward(ctx, gE)
+        return dx, dw, None, None, None, None, None, None, None
+
+
+def _qsim_noisy(x, w, be, noise, shots, T, seed, counter) -> torch.Tensor:
+    n, L = x.shape[1], w.shape[-3]
+    if be == "torch":
+        raise ValueError("the torch backend has no noise model; use hip or cpu")
+    if be == "hip":
+        if x.device.type != "cuda":
+            raise RuntimeError("hip backend needs CUDA/HIP tensors")
+        _hip_shots_limit(n)
+        _check_noise_shape(n, L)
+        if 2 * n * L > 256 and n > HIP_REG_MAX_QUBITS:   # (the adjoint's limit, as for the exact call)
+            raise NotImplementedError("large-n HIP simulator supports 2*n*L <= 256")
+        ctr0, cptr = _split_counter(counter, x.device)
+        return _QSimNoisyHIP.apply(x, w, wgroup_of(x, w), noise, shots, T, int(seed), ctr0, cptr)
+    if be == "cpu":
+        if x.device.type != "cpu":
+            raise RuntimeError("cpu backend needs CPU tensors")
+        _check_noise_shape(n, L)
+        ctr0, _ = _split_counter(counter, x.device)
+        E = _noisy_shots_cpu(x.detach().float().contiguous(), w.detach().float().contiguous(), noise, shots, T,
+                             int(seed), ctr0)
+        return _ReplaceValue.apply(qsim(x, w, "cpu"), E)
+    raise ValueError(f"unknown backend {be!r}")
 
 
 # ----------------------------------------------------------------------------- parameter shift
@@ -561,7 +820,8 @@ class _QSimPShift(torch.autograd.Function):
 
 
 def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots: Optional[int] = None, seed: int = 0,
-         counter=0, diff_method: str = "adjoint", shift_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+         counter=0, diff_method: str = "adjoint", shift_mask: Optional[torch.Tensor] = None,
+         noise: Optional["NoiseModel"] = None, trajectories: int = 1) -> torch.Tensor:
     """<Z_i> of the QSC circuit for inputs x (B, n) and weights w (L, n, 2).
 
     ``w`` may also be grouped, (G, L, n, 2) with B % G == 0: sample b then uses
@@ -579,12 +839,32 @@ def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots:
     angle shifted by +-pi/2, each measured with the forward's ``shots`` (None: exactly) -- csrc/hip/qsim_pshift.hip.
     Shifted circuit (p, s) draws under counter + ((1 + 2p + s) << 48), so its shots never coincide with the
     forward's or another circuit's for counters below 2^48.  ``shift_mask`` ((L, n, 2) bool, None: all): the
-    parameters whose circuits run; the others get a gradient of exactly 0 (``x``'s gradient is unaffected)."""
+    parameters whose circuits run; the others get a gradient of exactly 0 (``x``'s gradient is unaffected).
+
+    ``noise`` (a ``NoiseModel``; needs ``shots``; ``hip`` with n <= 12, or ``cpu``): the shots are measured on a
+    device with Pauli gate errors and readout error -- csrc/hip/qsim_noise.hip.  The shots are split evenly over
+    ``trajectories`` (1 .. 1024) independent realisations of the gate errors; trajectory t owns shots
+    [t shots/T, (t+1) shots/T), and for T > 1 shots / T must be a multiple of 4.  With all rates zero the result is
+    bit-identical to the noiseless ``shots`` call.  The backward stays the exact adjoint of the noiseless circuit
+    (straight-through); ``diff_method="parameter_shift"`` is not available under noise."""
     _check_shapes(x, w)
     n = x.shape[1]
     be = backend if backend not in (None, "auto") else default_backend(x.device)
     if diff_method not in DIFF_METHODS:
         raise ValueError(f"unknown diff_method {diff_method!r}: one of {DIFF_METHODS}")
+    if noise is not None:
+        if not isinstance(noise, NoiseModel):
+            raise ValueError(f"noise must be a NoiseModel, got {type(noise).__name__}")
+        if not shots:
+            raise ValueError("noise needs shots: the noise model is sampled per measurement shot")
+        if diff_method != "adjoint":
+            raise ValueError("noise with diff_method='parameter_shift' is not supported")
+        if shift_mask is not None:
+            raise ValueError("shift_mask needs diff_method='parameter_shift'")
+        shots = _check_shots(shots)
+        return _qsim_noisy(x, w, be, noise, shots, _check_trajectories(shots, trajectories), seed, counter)
+    if int(trajectories) != 1:
+        raise ValueError("trajectories needs noise")
     if diff_method == "parameter_shift":
         if be == "torch":
             raise ValueError("the torch backend has no parameter-shift rule; use hip or cpu")

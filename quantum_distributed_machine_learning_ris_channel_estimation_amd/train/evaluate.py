@@ -92,10 +92,25 @@ class model_val:
         self.device = resolve_device(cfg.device)
         self.epoch_tag = "epoch99"
         self.hip_engine = True   # (GPU) the HIP inference engine; False: the models' torch forward
+        self._qsc_noise = None
+        self.qsc_noise_model()   # (refuses noise rates without qsc_shots)
         self.results: Dict[str, List[float]] = {}
 
     def load_model_state_dict(self, model, filepath, fallback_key=None):
         ck.load_model_state_dict(model, filepath, fallback_key, map_location=self.device)
+
+    def qsc_noise_model(self):
+        """The ``NoiseModel`` of the qsc_noise_* / qsc_readout* knobs (None: all rates zero); it needs qsc_shots."""
+        rates = (float(self.qsc_noise_p1), float(self.qsc_noise_p2), float(self.qsc_readout01),
+                 float(self.qsc_readout10))
+        if not any(rates):
+            return None
+        if int(self.qsc_shots) <= 0:
+            raise ValueError("qsc_noise_* / qsc_readout* need qsc_shots > 0: the noise model is sampled per shot")
+        if self._qsc_noise is None or self._qsc_noise[0] != rates:
+            from ..ops.quantum import NoiseModel
+            self._qsc_noise = (rates, NoiseModel(*rates))
+        return self._qsc_noise[1]
 
     # ------------------------------------------------------------------ loading
     def _dir(self) -> str:
@@ -141,6 +156,7 @@ class model_val:
     def evaluate_snr(self, snr: float, sc, qsc, convs, fc, chunk: int = 4096) -> Dict[str, float]:
         dev = self.device
         criterion = NMSELoss()
+        self.qsc_noise_model()   # (a noise rate without qsc_shots is an error, not a silently exact sweep)
         Yp, HLS, H, ind = generate_mixed(self.data_len_for_test, float(snr), self.Pilot_num, self.indicator,
                                          base_seed=self.seed, split=f"test@{self.training_data_len * 3}", device=dev)
         # FIG1's "MMSE" row: the reference-calibrated subspace estimator (~LS - 1.3 dB at every SNR, the
@@ -159,20 +175,23 @@ class model_val:
                 continue
             # qsc_shots > 0: the quantum SC's circuit is measured with that many shots per sample (seeded by cfg.seed)
             shots = int(self.qsc_shots) if tag == "quantum" and getattr(clf, "use_quantum", False) else 0
+            noise = self.qsc_noise_model() if shots else None
+            traj = int(self.qsc_trajectories) if noise is not None else 1
             if eng is not None and (eng.sc if tag == "classical" else eng.qsc) is not None:
                 # the HIP kernels: classifier, experts, routed FC (train/infer.py)
-                pred = eng.classify(x, tag, shots=shots, seed=self.seed) if shots else eng.classify(x, tag)
+                pred = (eng.classify(x, tag, shots=shots, seed=self.seed, noise=noise, trajectories=traj) if shots
+                        else eng.classify(x, tag))
             else:   # (CPU, or the classical-fallback QSC ablation: torch)
                 if shots:
                     ql = clf.qlayer
-                    exact = (ql.shots, ql.shot_seed, ql._shot_calls)
-                    ql.shots = shots
+                    exact = (ql.shots, ql.shot_seed, ql._shot_calls, ql.noise, ql.trajectories)
+                    ql.shots, ql.noise, ql.trajectories = shots, noise, traj
                     ql.manual_shot_seed(self.seed)
                 try:
                     pred = torch.cat([clf(x[i:i + chunk]).argmax(1) for i in range(0, x.shape[0], chunk)])
                 finally:
                     if shots:
-                        ql.shots, ql.shot_seed, ql._shot_calls = exact
+                        ql.shots, ql.shot_seed, ql._shot_calls, ql.noise, ql.trajectories = exact
             saved = None
             if self.bn_adapt:   # (GPU: the HIP training conv forward computes the statistics, no MIOpen)
                 saved = eng.recalibrate_bn(convs, x, pred) if eng is not None else recalibrate_bn(convs, x, pred)
@@ -251,6 +270,9 @@ class model_val:
             "Accuracy_Classical": list(map(float, acc_classical)),
             "Accuracy_Quantum": list(map(float, acc_quantum)),
             "qsc_shots": int(self.qsc_shots),   # (0: exact expectation values)
+            "qsc_noise_p1": float(self.qsc_noise_p1), "qsc_noise_p2": float(self.qsc_noise_p2),
+            "qsc_readout01": float(self.qsc_readout01), "qsc_readout10": float(self.qsc_readout10),
+            "qsc_trajectories": int(self.qsc_trajectories),
         }
         if nmse_lmmse is not None:
             results["NMSE_LMMSE_dB"] = db(nmse_lmmse)

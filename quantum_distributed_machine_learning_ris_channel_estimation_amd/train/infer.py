@@ -158,12 +158,16 @@ class HIPInference:
                                self.chunk, self._plane, st), "gather(xq)")
 
     @torch.no_grad()
-    def classify(self, x: torch.Tensor, which: str, shots: int = 0, seed: int = 0) -> torch.Tensor:
+    def classify(self, x: torch.Tensor, which: str, shots: int = 0, seed: int = 0, noise=None,
+                 trajectories: int = 1) -> torch.Tensor:
         """Predicted scenario (N,) int64 of every sample with the classical ("classical") or quantum SC.
         ``shots`` > 0 ("quantum" only): the circuit is measured with that many shots per sample; the shot
-        stream is keyed by ``seed`` and the chunk index (the counter), the sample's row within its chunk."""
+        stream is keyed by ``seed`` and the chunk index (the counter), the sample's row within its chunk.
+        ``noise`` / ``trajectories`` (with ``shots``): measured under that ``ops.quantum.NoiseModel``."""
         if shots and which != "quantum":
             raise ValueError("shots apply to the quantum classifier only")
+        if noise is not None and not shots:
+            raise ValueError("noise needs shots")
         clf = self.sc if which == "classical" else self.qsc
         assert clf is not None, f"no {which} classifier loaded"
         x = x.contiguous().float()
@@ -175,7 +179,8 @@ class HIPInference:
             if which == "classical":
                 self.sc.forward(self.xq, self.pred)
             else:
-                self.qsc.infer(self.xq, self.pred, shots=shots, seed=seed, counter=lo // self.chunk)
+                self.qsc.infer(self.xq, self.pred, shots=shots, seed=seed, counter=lo // self.chunk, noise=noise,
+                               trajectories=trajectories)
             out[lo:lo + n].copy_(self.pred[:n])
         return out
 
