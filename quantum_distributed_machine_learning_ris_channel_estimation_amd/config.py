@@ -77,6 +77,18 @@ class RunnerConfig:
     # per epoch end), with every expert's BN statistics re-estimated on its training streams, saved beside the
     # epoch checkpoints under the tag "swa" (0: off; the reference evaluates the last epoch's weights)
     swa_epochs: int = 0
+    # on-chip QSC training (train-qsc; EvalConfig's names): the backward of the quantum layer (ops/quantum.py
+    # DIFF_METHODS: adjoint | parameter_shift | on_chip), the measurement shots per circuit (0: exact), and the
+    # device noise the shots are measured under (needs qsc_shots > 0): Pauli error rate per fused one-qubit gate /
+    # per CNOT, readout error 0 -> 1 / 1 -> 0, gate-error realisations the shots are split over.  Anything but the
+    # defaults trains through the module path (no fused step, no graph capture), world size 1 only.
+    qsc_diff_method: str = "adjoint"
+    qsc_shots: int = 0
+    qsc_noise_p1: float = 0.0
+    qsc_noise_p2: float = 0.0
+    qsc_readout01: float = 0.0
+    qsc_readout10: float = 0.0
+    qsc_trajectories: int = 1
 
     def update_from_dict(self, d: Dict[str, Any]) -> "RunnerConfig":
         names = {f.name: f for f in dataclasses.fields(self)}

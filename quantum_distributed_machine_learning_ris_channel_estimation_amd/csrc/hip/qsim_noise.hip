@@ -35,141 +35,10 @@
 //           i >> 3, b, lo32(c), hi32(c)); field = (word[(i & 7) >> 1] >> 16 (i & 1)) & 0xFFFF; the bit, taken after
 //           the frame XOR, flips iff field < thr_ro[i][bit]  (bit = 0: readout01, bit = 1: readout10)
 //   c1, E, counts as in qsim_shots.hip.  With every threshold 0, E and counts are those of qd_qsim_shots_fwd.
-#include "qsim_shots_dev.h"
+#include "qsim_noise_dev.h"
 
 namespace qd {
 namespace qnoise {
-
-using namespace qd::qshots;
-
-constexpr int kMaxTraj = 1024;
-constexpr int kMaxSites = 4096;
-constexpr int kLdsBudget = 40 * 1024;   // a quarter of a CU's LDS: what a workgroup may take and still be one of four
-__host__ __device__ constexpr size_t traj_bytes(int T) { return sizeof(uint16_t) * (((size_t)T + 7) & ~(size_t)7); }
-constexpr uint16_t kRebuild = 0x8000;   // traj word: bit 15 = a frame before the last layer is not identity; low bits = the last layer's X mask
-
-struct Rng {
-  uint32_t b, c_lo, c_hi, k0, k1;
-};
-
-// (x, z) bits of a one-qubit Pauli code 0 .. 3 = I, X, Y, Z
-__device__ __forceinline__ uint32_t pauli_x(uint32_t p) { return ((p + 1u) >> 1) & 1u; }
-__device__ __forceinline__ uint32_t pauli_z(uint32_t p) { return (p >> 1) & 1u; }
-
-// floor(r m / thr) for r < thr, without a 64-bit division: the number of multiples of thr that are <= r m
-template <int M>
-__device__ __forceinline__ uint32_t scaled_code(uint32_t r, uint32_t thr) {
-  const unsigned long long v = (unsigned long long)r * M;
-  uint32_t q = 0;
-#pragma unroll
-  for (int i = 1; i < M; ++i) q += v >= (unsigned long long)thr * i ? 1u : 0u;
-  return q;
-}
-
-// The Pauli frame (fa, fb) of layer l of trajectory tau.
-template <int N>
-__device__ __forceinline__ void layer_frame(int l, uint32_t tau, const Rng& g, const uint32_t* __restrict__ thr1,
-                                            const uint32_t* __restrict__ thr2, int& fa, int& fb) {
-  uint32_t a = 0, z = 0, code2[N];
-  Philox ph = {{0u, 0u, 0u, 0u}};
-#pragma unroll
-  for (int q = 0; q < N; ++q) {
-    const uint32_t s0 = (uint32_t)(l * N + q) * 2u;   // k = 0; k = 1 is s0 + 1, in the same Philox block
-    if (q == 0 || (s0 & 3u) == 0u) ph = philox4x32_10(0x80000000u | (tau << 10) | (s0 >> 2), g.b, g.c_lo, g.c_hi, g.k0, g.k1);
-    const uint32_t r0 = (s0 & 2u) ? ph.c[2] : ph.c[0], r1 = (s0 & 2u) ? ph.c[3] : ph.c[1];
-    const uint32_t t1 = thr1[q], t2 = thr2[q];
-    const uint32_t c0 = r0 < t1 ? 1u + scaled_code<3>(r0, t1) : 0u;
-    code2[q] = r1 < t2 ? 1u + scaled_code<15>(r1, t2) : 0u;
-    a |= pauli_x(c0) << q;
-    z |= pauli_z(c0) << q;
-  }
-#pragma unroll
-  for (int c = 0; c < N; ++c) {
-    const int t = (c + 1) % N;
-    a ^= ((a >> c) & 1u) << t;
-    z ^= ((z >> t) & 1u) << c;
-    const uint32_t pc = code2[c] >> 2, pt = code2[c] & 3u;
-    a ^= (pauli_x(pc) << c) ^ (pauli_x(pt) << t);
-    z ^= (pauli_z(pc) << c) ^ (pauli_z(pt) << t);
-  }
-  fa = (int)a;
-  fb = (int)z;
-}
-
-// The four shots of Philox block j (shots 4 j .. 4 j + 3) of an `active` lane: outcome from the CDF, the frame's X
-// mask, readout flips, then the wave's bit counts into acc.  Every lane of the wave calls it.
-template <int N>
-__device__ __forceinline__ void draw_block(const uint32_t* cdf, uint32_t tot, uint32_t j, bool active, int shots,
-                                           uint32_t amask, bool readout, const uint32_t* __restrict__ thr_ro,
-                                           const Rng& g, uint32_t (&acc)[N]) {
-  constexpr int D = 1 << N;
-  Philox ph = {{0u, 0u, 0u, 0u}};
-  if (active) ph = philox4x32_10(j, g.b, g.c_lo, g.c_hi, g.k0, g.k1);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const uint32_t s = 4u * j + r;
-    const bool valid = active && s < (uint32_t)shots;
-    const uint32_t t = __umulhi(ph.c[r], tot);
-    int k = 0;
-#pragma unroll
-    for (int step = D >> 1; step >= 1; step >>= 1)
-      if (cdf[cdf_at(k + step - 1)] <= t) k += step;
-    k ^= (int)amask;
-    if (readout && valid) {
-#pragma unroll
-      for (int h = 0; h < (N + 7) / 8; ++h) {
-        const Philox pr = philox4x32_10(0x40000000u | (s << 1) | (uint32_t)h, g.b, g.c_lo, g.c_hi, g.k0, g.k1);
-        int flip = 0;
-#pragma unroll
-        for (int i = 8 * h; i < N && i < 8 * h + 8; ++i) {
-          const uint32_t field = (pr.c[(i & 7) >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-          const uint32_t t01 = thr_ro[2 * i], t10 = thr_ro[2 * i + 1];
-          flip |= (field < (((k >> i) & 1) ? t10 : t01) ? 1 : 0) << i;
-        }
-        k ^= flip;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) acc[i] += (uint32_t)__popcll(__ballot(valid && ((k >> i) & 1)));
-  }
-}
-
-// A pass's wave-uniform bit counts into the wave's own row of wcnt (only lane 0 of that wave ever touches the row, so
-// no barrier is needed until the rows are summed); the counts then start again from zero.
-template <int N>
-__device__ __forceinline__ void flush_counts(uint32_t* wcnt, uint32_t (&acc)[N]) {
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) wcnt[(threadIdx.x >> 6) * N + i] += acc[i];
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) acc[i] = 0;
-}
-
-// The state in A -> fp32 probabilities (to probs when non-null) -> quantised words over the state -> scanned CDF.
-template <int N>
-__device__ __forceinline__ uint32_t state_to_cdf(cf* A, uint32_t* wtot, float* __restrict__ probs) {
-  constexpr int D = 1 << N;
-  constexpr int PER = D >= NT ? D / NT : 1;
-  uint32_t* cdf = reinterpret_cast<uint32_t*>(A);
-  uint32_t q[PER];
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const int k = threadIdx.x + i * NT;
-    if (k < D) {
-      const float p = prob_of(A[k]);
-      if (probs != nullptr) probs[k] = p;
-      q[i] = quantise(p);
-    }
-  }
-  __syncthreads();   // every amplitude has been read: the CDF may overwrite the state
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const int k = threadIdx.x + i * NT;
-    if (k < D) cdf[cdf_at(k)] = q[i];
-  }
-  return cdf_scan<N>(cdf, wtot);
-}
 
 // (waves_per_eu 4: at n = 12 the state's 32 KiB let four workgroups share a CU, so the registers must too)
 // CACHE: the frames of layers 0 .. L-2 of every trajectory are kept in LDS (a | b << 16; T (L - 1) words) for the

@@ -25,97 +25,21 @@
 // caller keeps the masked dw[p] at 0).
 #include <algorithm>
 
-#include "qsim_shots_dev.h"
+#include "qsim_pshift_dev.h"
 
 namespace qd {
 namespace qpshift {
-using namespace qd::qshots;
 
 // LDS carve (bytes): qsim_shots.hip's (trig | scan totals | per-wave bit counts), then gE of the sample (<= 12
 // floats) | E+ and E- of the parameter at hand (2 x 12 floats) | the working state, later its CDF | (n <= 11) the
 // state that enters the layer
 constexpr int O_GE = 512, O_EPM = 576, O_STATE = 768;
 template <int N>
-constexpr bool reg_prefix() {
-  return N >= 12;
-}
-template <int N>
 constexpr size_t smem_bytes() {
   return O_STATE + (reg_prefix<N>() ? 1 : 2) * sizeof(cf) * (1 << N);
 }
 
-constexpr float kHalfPi = 1.57079632679489661923f;
 constexpr int kTargetBlocks = 8192;   // workgroups a launch is split towards: some rounds of 256 CUs x 2 .. 8 each
-
-// qubits per LDS round trip of a layer's pair sweeps: three leave lanes idle below 512 amplitudes
-template <int N>
-constexpr int group_bits() {
-  return N >= 9 ? 3 : 2;
-}
-
-// A thread's share of a layer's first pair sweep (qubits 0 .. NB-1): tasks t = threadIdx.x + it NT, 2^NB amplitudes
-// (t << NB) | j each
-template <int N>
-struct FirstSweep {
-  static constexpr int NB = N < group_bits<N>() ? N : group_bits<N>();
-  static constexpr int TASKS = (1 << N) >> NB;
-  static constexpr int TPT = TASKS >= NT ? TASKS / NT : 1;
-  static constexpr int AMPS = TPT << NB;
-};
-
-// the thread's share of the state in A, into registers
-template <int N>
-__device__ __forceinline__ void keep_state(cf* R, const cf* A) {
-  using F = FirstSweep<N>;
-#pragma unroll
-  for (int it = 0; it < F::TPT; ++it) {
-    const int t = threadIdx.x + it * NT;
-    if (t < F::TASKS) {
-#pragma unroll
-      for (int j = 0; j < (1 << F::NB); ++j) R[(it << F::NB) | j] = A[(t << F::NB) | j];
-    }
-  }
-}
-
-// the first pair sweep of a layer on the kept state, into A (what apply_layer's group 0 does from LDS); ends with a
-// barrier
-template <int N>
-__device__ __forceinline__ void first_sweep(const cf* R, cf* A, const float4* trig) {
-  using F = FirstSweep<N>;
-#pragma unroll
-  for (int it = 0; it < F::TPT; ++it) {
-    const int t = threadIdx.x + it * NT;
-    if (t < F::TASKS) {
-      cf a[1 << F::NB];
-#pragma unroll
-      for (int j = 0; j < (1 << F::NB); ++j) a[j] = R[(it << F::NB) | j];
-#pragma unroll
-      for (int b = 0; b < F::NB; ++b) {
-        const float4 tg = trig[b];
-#pragma unroll
-        for (int j = 0; j < (1 << F::NB); ++j)
-          if (!((j >> b) & 1)) gate_fwd(a[j], a[j | (1 << b)], tg);
-      }
-#pragma unroll
-      for (int j = 0; j < (1 << F::NB); ++j) A[(t << F::NB) | j] = a[j];
-    }
-  }
-  __syncthreads();
-}
-
-// layer_trig with one angle of the layer shifted: qubit sq's RY (sk = 0) or RZ (sk = 1) angle by sh; sq < 0: none
-__device__ __forceinline__ void layer_trig_shifted(float4* trig, const float* wl, const float* xs, int n, int sq, int sk,
-                                                   float sh) {
-  if (threadIdx.x < n) {
-    const int q = threadIdx.x;
-    const float th = wl[2 * q] + (xs ? xs[q] : 0.f) + (q == sq && sk == 0 ? sh : 0.f);
-    const float ph = wl[2 * q + 1] + (q == sq && sk == 1 ? sh : 0.f);
-    float s, c, sp, cp;
-    __sincosf(0.5f * th, &s, &c);
-    __sincosf(0.5f * ph, &sp, &cp);
-    trig[q] = make_float4(c, s, cp, sp);
-  }
-}
 
 template <int N>
 __global__ void __launch_bounds__(NT) qsim_pshift_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -136,7 +60,6 @@ __global__ void __launch_bounds__(NT) qsim_pshift_kernel(const float* __restrict
   float* epm = reinterpret_cast<float*>(smem + O_EPM);
   cf* A = reinterpret_cast<cf*>(smem + O_STATE);
   uint32_t* cdf = reinterpret_cast<uint32_t*>(smem + O_STATE);   // over the working state, once it has been read
-  constexpr int GB = group_bits<N>();
   const int chunk = blockIdx.x % chunks, l = (blockIdx.x / chunks) % L, b = blockIdx.x / (chunks * L);
   const int q0 = chunk * N / chunks, q1 = (chunk + 1) * N / chunks;   // this workgroup's qubits
   const int P = 2 * N * L;
@@ -162,35 +85,12 @@ __global__ void __launch_bounds__(NT) qsim_pshift_kernel(const float* __restrict
   cf* Pfx = RP ? A : A + D;
   cf pfx[RP ? FirstSweep<N>::AMPS : 1];
   if (l > 0) {
-    layer_trig(trig, wsmp, xs, N);
-    __syncthreads();
-    product_state<N>(Pfx, trig);
-    for (int m = 1; m < l; ++m) {
-      layer_trig(trig, wsmp + 2 * N * m, nullptr, N);
-      __syncthreads();
-      apply_layer<N, GB>(Pfx, Pfx, trig);
-    }
+    prefix_state<N>(Pfx, trig, wsmp, xs, l);
     if constexpr (RP) keep_state<N>(pfx, A);   // (a thread rewrites these amplitudes of A itself, in first_sweep)
   }
 
   // the final state, in A, of the circuit with layer l's angle (sq, sk) shifted by sh (sq < 0: the circuit itself)
-  auto make_state = [&](int sq, int sk, float sh) {
-    layer_trig_shifted(trig, wsmp + 2 * N * l, l == 0 ? xs : nullptr, N, sq, sk, sh);
-    __syncthreads();
-    if (l == 0) {
-      product_state<N>(A, trig);
-    } else if constexpr (RP) {
-      first_sweep<N>(pfx, A, trig);
-      apply_layer<N, GB, 1>(A, A, trig);
-    } else {
-      apply_layer<N, GB>(Pfx, A, trig);
-    }
-    for (int m = l + 1; m < L; ++m) {
-      layer_trig(trig, wsmp + 2 * N * m, nullptr, N);
-      __syncthreads();
-      apply_layer<N, GB>(A, A, trig);
-    }
-  };
+  auto make_state = [&](int sq, int sk, float sh) { shifted_state<N>(A, Pfx, pfx, trig, wsmp, xs, l, L, sq, sk, sh); };
   float pr[PER];   // the probabilities of the state in A, outcome threadIdx.x + i NT
   auto read_probs = [&]() {
 #pragma unroll

@@ -1,5 +1,6 @@
-// Device functions of the finite-shot kernels (qsim_shots.hip, qsim_pshift.hip, qsim_noise.hip): the LDS-resident
-// state build of the QSC circuit (FRAMED: with a Pauli frame behind a layer's ring, for qsim_noise.hip), the CDF scan,
+// Device functions of the finite-shot kernels (qsim_shots.hip, qsim_pshift.hip, qsim_noise.hip, qsim_onchip.hip): the
+// LDS-resident state build of the QSC circuit (FRAMED: with a Pauli frame behind a layer's ring, for the noisy
+// kernels), the CDF scan,
 // Philox4x32-10 and the outcome search.  The sampling contract they implement is stated at the top of qsim_shots.hip.
 #pragma once
 #include "common.h"

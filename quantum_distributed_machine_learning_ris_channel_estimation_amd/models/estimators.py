@@ -85,14 +85,15 @@ class QuantumLayer(nn.Module):
     every forward advances, so successive calls draw different shots; ``manual_shot_seed`` restarts it.
     Neither is a parameter or a buffer: the state_dict is that of the exact layer.
 
-    ``diff_method`` (settable; "adjoint" or "parameter_shift") selects the backward: the exact adjoint, or the
-    parameter-shift rule measured with the same ``shots`` (``qsim(diff_method=)``).  ``shift_mask`` (settable;
+    ``diff_method`` (settable; "adjoint", "parameter_shift" or "on_chip") selects the backward: the exact adjoint,
+    the parameter-shift rule measured with the same ``shots``, or with "on_chip" (needs ``shots``) that rule measured
+    under the same ``noise`` and ``trajectories`` as well (``qsim(diff_method=)``).  ``shift_mask`` (settable;
     None or a (n_layers, n_qubits, 2) bool tensor) names the parameters whose shifted circuits run; the others
     get a zero gradient.  Both are plain attributes too.
 
     ``noise`` (settable; None or an ``ops.quantum.NoiseModel``) and ``trajectories`` (settable; 1 .. 1024) measure
     the shots on a device with Pauli gate errors and readout error (``qsim(noise=, trajectories=)``); they need
-    ``shots``, and gradients stay those of the noiseless circuit."""
+    ``shots``, and gradients stay those of the noiseless circuit unless ``diff_method`` is "on_chip"."""
 
     def __init__(self, n_qubits: int, n_layers: int, backend: Optional[str] = None, shots: Optional[int] = None,
                  diff_method: str = "adjoint", noise=None, trajectories: int = 1):
@@ -145,8 +146,9 @@ class QSC_P128(nn.Module):
     defined there): Linear(n, n) + Tanh in place of the VQC, an equal-width classical ablation
     with the same (-1, 1) output range as <Z_i>.
     ``shots`` goes to the ``qlayer`` (finite-shot <Z_i>; None = exact), and so does ``diff_method``
-    ("adjoint", or "parameter_shift": the gradient an on-chip QNN measures), ``noise`` and ``trajectories``
-    (the device's gate and readout errors under which the shots are measured).
+    ("adjoint", "parameter_shift": the gradient an on-chip QNN measures, or "on_chip": that gradient measured
+    under ``noise`` too), ``noise`` and ``trajectories`` (the device's gate and readout errors under which the
+    shots are measured).
     """
 
     def __init__(self, n_qubits: int = 6, n_layers: int = 3, n_classes: int = 3, use_quantumnat: bool = True,

@@ -29,6 +29,10 @@ Device noise (``NoiseModel``, ``qsim(..., shots=N, noise=, trajectories=T)``, ``
 ``qsim_probs(frames=)``, ``sample_z_noisy``): the shots are measured under Pauli gate errors and readout error, the
 gate errors of each of T trajectories collapsed into one Pauli frame per layer -- csrc/hip/qsim_noise.hip (n <= 12)
 on ``hip``, composed from the C++ oracles of the same integer contract on ``cpu``; gradients stay straight-through.
+
+On-chip gradients (``qsim(..., shots=N, diff_method="on_chip", noise=, trajectories=T)``, ``pshift_rows(noise=)``):
+the parameter-shift rule with every shifted circuit measured on that noisy device under its own counter --
+csrc/hip/qsim_onchip.hip (n <= 12) on ``hip``, the noisy forward's host composition per circuit on ``cpu``.
 """
 from __future__ import annotations
 
@@ -689,7 +693,7 @@ def _qsim_noisy(x, w, be, noise, shots, T, seed, counter) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------- parameter shift
-DIFF_METHODS = ("adjoint", "parameter_shift")
+DIFF_METHODS = ("adjoint", "parameter_shift", "on_chip")
 PSHIFT_ID_SHIFT = 48   # circuit (p, s) draws under call counter c + (id << 48), id = 1 + 2p + s; the forward is id 0
 
 
@@ -729,9 +733,29 @@ def hip_qsim_pshift(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, G: torch
               "qd_qsim_pshift")
 
 
-def _pshift_rows_cpu(x, w, gE, mask, need_dx, shots, seed, ctr0) -> torch.Tensor:
+def hip_qsim_noisy_pshift(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, G: torch.Tensor,
+                          Epm: Optional[torch.Tensor] = None, probs: Optional[torch.Tensor] = None,
+                          mask: Optional[torch.Tensor] = None, need_dx: bool = True, shots: int = 0, seed: int = 0,
+                          ctr0: int = 0, counter_ptr=None, wgroup: int = 0, noise: Optional["NoiseModel"] = None,
+                          trajectories: int = 1, frames: Optional[torch.Tensor] = None) -> None:
+    """Raw launcher of csrc/hip/qsim_onchip.hip (n <= 12): ``hip_qsim_pshift`` with every shifted circuit measured
+    under ``noise`` over ``trajectories`` error realisations drawn under the circuit's own counter.  probs
+    (nullable) is (B, P, 2, T, 2^n) here, frames (nullable; B, P, 2, T, L, 2) int32 every trajectory's Pauli frames."""
+    B, n = x.shape
+    thr1, thr2, thr_ro = (noise if noise is not None else NoiseModel()).thresholds(n, x.device)
+    f = nat.fn(nat.hip_lib(), "qd_qsim_noisy_pshift",
+               [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _u64, _u64, _p, _p])
+    opt = lambda t: nat.ptr(t) if t is not None else None   # noqa: E731
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(gE), nat.ptr(G), opt(Epm), opt(probs), opt(frames), opt(mask),
+                nat.ptr(thr1), nat.ptr(thr2), nat.ptr(thr_ro), B, n, w.shape[-3], wgroup, int(need_dx), shots,
+                int(trajectories), seed & _M64, ctr0 & _M64, counter_ptr, nat.stream_ptr(x.device)),
+              "qd_qsim_noisy_pshift")
+
+
+def _pshift_rows_cpu(x, w, gE, mask, need_dx, shots, seed, ctr0, noise=None, T=1) -> torch.Tensor:
     """The kernel's G composed from the host oracles: qsim_probs (fp64) of the shifted weights, then sample_z under
-    the circuit's counter, or the probability-weighted sum in exact mode."""
+    the circuit's counter, or the probability-weighted sum in exact mode.  With ``noise``: the noisy forward's
+    composition (sites -> frames -> framed probabilities -> noisy sampler), all under the circuit's counter."""
     B, n = x.shape
     P = 2 * n * w.shape[-3]
     zs = z_signs(n, dtype=torch.float64)
@@ -744,6 +768,9 @@ def _pshift_rows_cpu(x, w, gE, mask, need_dx, shots, seed, ctr0) -> torch.Tensor
         for s, sh in enumerate((0.5 * math.pi, -0.5 * math.pi)):
             ws = w.clone()
             ws.view(-1, P)[:, p] += sh
+            if noise is not None:
+                E.append(_noisy_shots_cpu(x, ws, noise, shots, T, seed, pshift_counter(ctr0, p, s)).double())
+                continue
             pr = qsim_probs(x, ws, "cpu")
             E.append(sample_z(pr, shots, seed, pshift_counter(ctr0, p, s)).double() if shots else pr @ zs)
         G[:, p] = (g64 * (E[0] - E[1]) * 0.5).sum(1).float()
@@ -753,13 +780,24 @@ def _pshift_rows_cpu(x, w, gE, mask, need_dx, shots, seed, ctr0) -> torch.Tensor
 @torch.no_grad()
 def pshift_rows(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, backend: Optional[str] = None,
                 shots: Optional[int] = None, seed: int = 0, counter=0, shift_mask: Optional[torch.Tensor] = None,
-                need_dx: bool = True) -> torch.Tensor:
+                need_dx: bool = True, noise: Optional["NoiseModel"] = None, trajectories: int = 1) -> torch.Tensor:
     """Per-sample parameter-shift gradients G (B, 2nL) fp32 of sum(gE * qsim(x, w)): column p = (l n + q) 2 + k
-    is w[l, q, k]'s.  dx = G[:, 0:2n:2]; dw = G summed over the samples.  Arguments as for ``qsim``."""
+    is w[l, q, k]'s.  dx = G[:, 0:2n:2]; dw = G summed over the samples.  Arguments as for ``qsim``.  With
+    ``noise`` (needs ``shots``) every shifted circuit is measured on the noisy device, its gate errors, shots and
+    readout fields drawn under the circuit's own counter -- csrc/hip/qsim_onchip.hip."""
     _check_shapes(x, w)
     B, n = x.shape
     _check_pshift_shape(n, w.shape[-3])
     shots = _check_shots(shots) if shots else 0
+    if noise is not None:
+        if not isinstance(noise, NoiseModel):
+            raise ValueError(f"noise must be a NoiseModel, got {type(noise).__name__}")
+        if not shots:
+            raise ValueError("noise needs shots: the noise model is sampled per measurement shot")
+        trajectories = _check_trajectories(shots, trajectories)
+        _check_noise_shape(n, w.shape[-3])
+    elif int(trajectories) != 1:
+        raise ValueError("trajectories needs noise")
     be = backend if backend not in (None, "auto") else default_backend(x.device)
     x = x.detach().float().contiguous()
     w = w.detach().float().contiguous()
@@ -771,39 +809,44 @@ def pshift_rows(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, backend: Opt
         _hip_shots_limit(n)
         ctr0, cptr = _split_counter(counter, x.device)
         G = torch.empty(B, 2 * n * w.shape[-3], device=x.device, dtype=torch.float32)
-        if B > 0:
+        if B > 0 and noise is not None:
+            hip_qsim_noisy_pshift(x, w, gE, G, None, None, mask, need_dx, shots, int(seed), ctr0, cptr,
+                                  wgroup_of(x, w), noise, trajectories)
+        elif B > 0:
             hip_qsim_pshift(x, w, gE, G, None, None, mask, need_dx, shots, int(seed), ctr0, cptr, wgroup_of(x, w))
         return G
     if be == "cpu":
         if x.device.type != "cpu":
             raise RuntimeError("cpu backend needs CPU tensors")
         ctr0, _ = _split_counter(counter, x.device)
-        return _pshift_rows_cpu(x, w, gE, mask, need_dx, shots, int(seed), ctr0)
+        return _pshift_rows_cpu(x, w, gE, mask, need_dx, shots, int(seed), ctr0, noise, trajectories)
     if be == "torch":
         raise ValueError("the torch backend has no parameter-shift rule; use hip or cpu")
     raise ValueError(f"unknown backend {be!r}")
 
 
 class _QSimPShift(torch.autograd.Function):
-    """Forward: ``qsim``'s own (exact or finite-shot).  Backward: parameter shift with the forward's shots, seed
-    and counter (a device counter is read again by the backward: advance it after the backward)."""
+    """Forward: ``qsim``'s own (exact, finite-shot or noisy).  Backward: parameter shift with the forward's shots,
+    seed, counter, noise and trajectories (a device counter is read again by the backward: advance it after the
+    backward)."""
 
     @staticmethod
-    def forward(ctx, x, w, be, shots, seed, counter, shift_mask):
+    def forward(ctx, x, w, be, shots, seed, counter, shift_mask, noise=None, T=1):
         x = x.detach().float().contiguous()
         w = w.detach().float().contiguous()
         ctx.save_for_backward(x, w)
-        ctx.args = (be, shots, seed, counter, shift_mask)
-        return qsim(x, w, be, shots=shots, seed=seed, counter=counter)
+        ctx.args = (be, shots, seed, counter, shift_mask, noise, T)
+        return qsim(x, w, be, shots=shots, seed=seed, counter=counter, noise=noise, trajectories=T)
 
     @staticmethod
     def backward(ctx, gE):
         x, w = ctx.saved_tensors
-        be, shots, seed, counter, shift_mask = ctx.args
+        be, shots, seed, counter, shift_mask, noise, T = ctx.args
         B, n = x.shape
         L = w.shape[-3]
         P = 2 * n * L
-        G = pshift_rows(x, w, gE, be, shots, seed, counter, shift_mask, need_dx=ctx.needs_input_grad[0])
+        G = pshift_rows(x, w, gE, be, shots, seed, counter, shift_mask, need_dx=ctx.needs_input_grad[0], noise=noise,
+                        trajectories=T)
         dx = G[:, 0:2 * n:2].contiguous()
         if be == "hip" and B > 0:   # deterministic: no float atomics
             dw = torch.empty(P, device=x.device, dtype=torch.float32)
@@ -816,7 +859,7 @@ class _QSimPShift(torch.autograd.Function):
         dw = dw.view(L, n, 2)
         if w.dim() == 4:
             dw = _group_grad(dw, w)
-        return dx, dw, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None, None
 
 
 def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots: Optional[int] = None, seed: int = 0,
@@ -846,7 +889,14 @@ def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots:
     ``trajectories`` (1 .. 1024) independent realisations of the gate errors; trajectory t owns shots
     [t shots/T, (t+1) shots/T), and for T > 1 shots / T must be a multiple of 4.  With all rates zero the result is
     bit-identical to the noiseless ``shots`` call.  The backward stays the exact adjoint of the noiseless circuit
-    (straight-through); ``diff_method="parameter_shift"`` is not available under noise."""
+    (straight-through); ``diff_method="parameter_shift"`` is not available under noise.
+
+    ``diff_method="on_chip"`` (needs ``shots``; ``hip`` with n <= 12, or ``cpu``): the gradient a device reports.
+    The forward is the call's own (noisy shots with ``noise``, else plain shots); the backward is the
+    parameter-shift rule with every shifted circuit measured with the same ``shots``, ``noise`` and
+    ``trajectories``, its error sites, shots and readout fields drawn under its own counter
+    counter + ((1 + 2p + s) << 48) -- csrc/hip/qsim_onchip.hip.  ``shift_mask`` is allowed; with ``noise=None`` it
+    is ``"parameter_shift"`` bit for bit."""
     _check_shapes(x, w)
     n = x.shape[1]
     be = backend if backend not in (None, "auto") else default_backend(x.device)
@@ -857,26 +907,35 @@ def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots:
             raise ValueError(f"noise must be a NoiseModel, got {type(noise).__name__}")
         if not shots:
             raise ValueError("noise needs shots: the noise model is sampled per measurement shot")
-        if diff_method != "adjoint":
-            raise ValueError("noise with diff_method='parameter_shift' is not supported")
-        if shift_mask is not None:
-            raise ValueError("shift_mask needs diff_method='parameter_shift'")
+        if diff_method == "parameter_shift":
+            raise ValueError("noise with diff_method='parameter_shift' is not supported: "
+                             "diff_method='on_chip' measures the shifted circuits under the noise")
+        if shift_mask is not None and diff_method != "on_chip":
+            raise ValueError("shift_mask needs diff_method='parameter_shift' or 'on_chip'")
         shots = _check_shots(shots)
-        return _qsim_noisy(x, w, be, noise, shots, _check_trajectories(shots, trajectories), seed, counter)
-    if int(trajectories) != 1:
+        T = _check_trajectories(shots, trajectories)
+        if diff_method == "adjoint":
+            return _qsim_noisy(x, w, be, noise, shots, T, seed, counter)
+    elif int(trajectories) != 1:
         raise ValueError("trajectories needs noise")
-    if diff_method == "parameter_shift":
+    if diff_method in ("parameter_shift", "on_chip"):
         if be == "torch":
             raise ValueError("the torch backend has no parameter-shift rule; use hip or cpu")
         if be not in ("hip", "cpu"):
             raise ValueError(f"unknown backend {be!r}")
+        if diff_method == "on_chip" and not shots:
+            raise ValueError("diff_method='on_chip' needs shots: a device measures every circuit with finite shots")
         if be == "hip" and x.device.type == "cuda":
             _hip_shots_limit(n)
         _check_pshift_shape(n, w.shape[-3])
         _mask_u8(shift_mask, w)
-        return _QSimPShift.apply(x, w, be, _check_shots(shots) if shots else None, int(seed), counter, shift_mask)
+        shots = _check_shots(shots) if shots else None
+        if noise is None:
+            return _QSimPShift.apply(x, w, be, shots, int(seed), counter, shift_mask)
+        _check_noise_shape(n, w.shape[-3])
+        return _QSimPShift.apply(x, w, be, shots, int(seed), counter, shift_mask, noise, T)
     if shift_mask is not None:
-        raise ValueError("shift_mask needs diff_method='parameter_shift'")
+        raise ValueError("shift_mask needs diff_method='parameter_shift' or 'on_chip'")
     if shots:
         shots = _check_shots(shots)
         if be == "torch":

@@ -524,9 +524,31 @@ class Y2HRunner:
         ctx.heartbeat()
         return out
 
+    def qsc_device_knobs(self) -> Optional[Dict]:
+        """The QSC_P128 arguments of the qsc_* knobs (diff_method, shots, noise, trajectories), or None with the
+        defaults.  A noise rate needs qsc_shots, as in evaluation; these knobs train at world size 1 only."""
+        rates = (float(self.qsc_noise_p1), float(self.qsc_noise_p2), float(self.qsc_readout01),
+                 float(self.qsc_readout10))
+        shots, dm = int(self.qsc_shots), str(self.qsc_diff_method)
+        if any(rates) and shots <= 0:
+            raise ValueError("qsc_noise_* / qsc_readout* need qsc_shots > 0: the noise model is sampled per shot")
+        if dm == "adjoint" and shots <= 0 and int(self.qsc_trajectories) == 1:
+            return None
+        from ..ops.quantum import DIFF_METHODS, NoiseModel
+        if dm not in DIFF_METHODS:
+            raise ValueError(f"unknown qsc_diff_method {dm!r}: one of {DIFF_METHODS}")
+        if dm == "on_chip" and shots <= 0:
+            raise ValueError("qsc_diff_method=on_chip needs qsc_shots > 0: a device measures with finite shots")
+        if self._context().world > 1:
+            raise ValueError("qsc_diff_method / qsc_shots / qsc_noise_* train at world size 1 only")
+        return {"diff_method": dm, "shots": shots if shots > 0 else None,
+                "noise": NoiseModel(*rates) if any(rates) else None, "trajectories": int(self.qsc_trajectories)}
+
     def _train_classifier(self, model, kind: str, opt_name: str, wd: float, prune_thr: float,
-                          on_epoch, histories: Tuple[List, List, List], extra: Optional[Dict] = None):
-        """``extra``: small mutable trainer state (e.g. best accuracy) saved in the resume file."""
+                          on_epoch, histories: Tuple[List, List, List], extra: Optional[Dict] = None,
+                          module_path: bool = False):
+        """``extra``: small mutable trainer state (e.g. best accuracy) saved in the resume file.  ``module_path``:
+        train through the model's own forward and autograd, ungraphed (the fused step does not cover shots)."""
         ctx = self._context()
         tr, va = self.device_stores()
         model = model.to(ctx.device)
@@ -539,7 +561,7 @@ class Y2HRunner:
         S, B = tr.n_streams, self.batch_size_DML
         ref = self._dp_reference()
         Bl = (B + ctx.world - 1) // ctx.world if ref else B
-        cstep = ClassifierStep(model, S, space=space, batch_total=S * Bl)
+        cstep = ClassifierStep(model, S) if module_path else ClassifierStep(model, S, space=space, batch_total=S * Bl)
         skip = cstep.skip if self.nan_guard else None
         buckets = GradBuckets(ctx, {"all": [space.grad] + ([skip] if skip is not None else [])})
         cstep.grad_hook = buckets.launch
@@ -578,7 +600,7 @@ class Y2HRunner:
             buckets.wait()
             opt.step(grad_scale=gscale, skip=skip)
 
-        graphed = GraphedStep(lambda: run(static_idx), enabled=self._graphs_on())
+        graphed = GraphedStep(lambda: run(static_idx), enabled=self._graphs_on() and not module_path)
         sampler = DeviceSampler(tr.n, B, ctx.device, self.seed + 17, 0 if ref else ctx.rank)
         log = self._log()
         train_losses, val_losses, val_accs = histories
@@ -650,7 +672,10 @@ class Y2HRunner:
         model = QSC_P128(self.n_qubits, self.n_layers, self.n_classes, use_quantumnat=self.use_quantumnat,
                          use_gradient_pruning=self.use_gradient_pruning, pilot_num=self.Pilot_num,
                          backend=None if self.backend == "auto" else self.backend, noise_level=self.noise_level,
-                         gradient_threshold=self.gradient_threshold)
+                         gradient_threshold=self.gradient_threshold, **(self.qsc_device_knobs() or {}))
+        on_chip = self.qsc_device_knobs() is not None
+        if on_chip:
+            model.qlayer.manual_shot_seed(self.seed)   # the shot streams follow the run's seed
         ctx = self._context()
         d = ck.ckpt_dir(self.workspace, self.Pilot_num) if ctx.is_main else None
         state = {"best": 0.0}
@@ -669,7 +694,7 @@ class Y2HRunner:
         prune = self.gradient_threshold if self.use_gradient_pruning else 0.0
         self.qsc_model = self._train_classifier(model, "qsc", "adamw", self.qsc_weight_decay, prune, on_epoch,
                                                 (self.train_QSC_losses, self.val_QSC_losses, self.val_QSC_accuracies),
-                                                extra=state)
+                                                extra=state, module_path=on_chip)
         return self.qsc_model
 
     def train_SC_P128(self):
