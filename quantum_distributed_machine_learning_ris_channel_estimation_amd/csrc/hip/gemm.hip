@@ -43,6 +43,9 @@
 //             powers (dens), and per-tile column sums of dY (the bias gradient's partials) -- so
 //             the loss finish and the bias reduction run exactly as after csrc/hip/nmse.hip's
 //             one-pass kernel (qd_nmse_finish, or deferred into a later launch of the step).
+//             On the producer-wave forward tile (cfg 8) the producers prefetch the label rows during the K loop
+//             and run the row pass (NmsePrefetch): Y is rounded to bf16 first and the column sums come per chunk
+//             of 4 E rows, so dY and the bias gradient are bit-identical to the plain forward + that kernel.
 #include <type_traits>
 
 #include "common.h"
@@ -165,7 +168,12 @@ struct Geo {
   static constexpr int PA = A_BYTES / 1024, PB = B_BYTES / 1024, P = PA + PB;   // 1-KiB pieces per tile
   static constexpr int NPER = (P + NLD - 1) / NLD;    // pieces each loading wave issues per tile
   static constexpr int PITCH = BN + 4;               // fp32 epilogue tile row pitch
-  static constexpr int LDS = (NSTAGE * STAGE > BM * PITCH * 4 + 8192) ? NSTAGE * STAGE : BM * PITCH * 4 + 8192;
+  // PFQ: the tile whose producer waves prefetch the loss epilogue's label / perfect-channel rows (NmsePrefetch): four
+  // producers x 3 batches of 12 rows.  Its per-stream coefficients live in 256 bytes past the ring (CF_OFF): the
+  // producers write them while the compute waves still read the stages.
+  static constexpr bool PFQ = PW == 4 && BM == 144 && BN == 128 && F8 == 0 && KS == 1 && !ADIR;
+  static constexpr int LDS0 = (NSTAGE * STAGE > BM * PITCH * 4 + 8192) ? NSTAGE * STAGE : BM * PITCH * 4 + 8192;
+  static constexpr int CF_OFF = LDS0, LDS = LDS0 + (PFQ ? 256 : 0);
   static_assert(LA == KC || LA == KCD || BM % 128 == 0, "MC operand tiles are whole 128-column panels");
   static_assert(LB == KC || BN % 128 == 0, "MC operand tiles are whole 128-column panels");
   static_assert(BN % 128 == 0, "epilogue rows are 2 or 4 columns per lane");
@@ -203,6 +211,11 @@ __device__ __forceinline__ void vm_wait(int tiles) {   // leave `tiles` tiles of
   else if (tiles == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * N) : "memory");
   else if (tiles == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+template <int C>
+__device__ __forceinline__ void vm_wait_n() {   // leave C vector-memory loads in flight
+  static_assert(C >= 0 && C < 64, "vmcnt is 6 bits");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C) : "memory");
 }
 
 // LDS reads as inline asm: the compiler's own LDS wait counting turned conservative in this loop
@@ -422,6 +435,238 @@ struct Args {
   const float* deq2;    // nullable: with deq, the scales are deq[0] and deq2[0] (two separate scale slots)
   BnRedEpi br;          // EPI_BF16: nullable BN backward reduction (see BnRedEpi)
 };
+
+// EPI_NMSE on a Geo::PFQ tile: the producer waves fetch the tile's label and perfect-channel rows into registers
+// while the K loop runs and, instead of ending, run the loss's row pass from them after it (gemm_kernel's epilogue).
+// The K loop is fed from L2 and leaves HBM idle, so the round trip and the streaming of 147 KB per tile -- what made
+// the compute waves' epilogue cost as much as the NMSE launch it replaced -- hide behind the MFMAs.
+// Producer pw owns tile rows pw * 12 + 48 it + q (batch it < 3, q < 12).  One load instruction covers a row pair --
+// lanes 0-31 row 2 i, lanes 32-63 row 2 i + 1 of the batch -- at 4 columns (16 bytes) per lane: 18 pairs x (label,
+// perf) = 36 loads, 144 VGPRs per lane.  rowoff: one load, row j's in lane j, read back lane by lane.
+// The loads are inline asm: the compiler keeps no vmcnt book for them, the ring's waits are counted by hand (loads
+// retire in order; see the producer branch of gemm_kernel).  The asm ties each register as read-write, so a
+// conditional issue leaves no copy of a value still in flight, and nothing reads a register before wait(), which
+// passes every one of them through an asm after vmcnt(0).
+struct NoPrefetch {};
+template <class G>
+struct NmsePrefetch {
+  static constexpr int RB = 12, NB = G::BM / (G::PW * RB), NL = NB * RB / 2;   // rows per batch, batches, row pairs
+  static constexpr int Q = 2;                                                  // loads per issue<S>()
+  static_assert(G::BM == G::PW * RB * NB && G::BN == 128, "producers x batches of 12 rows, 32 lanes x 4 columns");
+  f32x4 l[NL], p[NL];
+  int ro[2 * NL];     // (wave-uniform)
+  int rv;
+  const float* lab;   // (+ this lane's column)
+  const float* per;   // (no perfect channel: the label again -- the load count stays fixed, the values unused)
+  int N;
+  bool hi;            // lanes 32-63: the odd row of each pair
+  int hm;             // (hi as 0 / 1)
+  __device__ __forceinline__ void init(const NmseArgs& na, int i0, int j0, int n, int pw, int lane) {
+    hi = lane >= 32;
+    hm = lane >> 5;
+    N = n;
+    const int col = j0 + (lane & 31) * 4;
+    lab = na.label + col;
+    per = (na.perf ? na.perf : na.label) + col;
+    // rowoff of the wave's row j in lane j: the first load of the wave, so the ring prologue's wait completes it
+    const int j = lane < 2 * NL ? lane : 2 * NL - 1;
+    rv = 0;
+    asm volatile("global_load_dword %0, %1, off"
+                 : "+v"(rv)
+                 : "v"(na.rowoff + i0 + pw * RB + (j / RB) * (G::PW * RB) + j % RB)
+                 : "memory");
+#pragma unroll
+    for (int s = 0; s < NL; ++s) l[s] = p[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  // after a wait that completed the rowoff load: the rows' offsets as wave-uniform values
+  __device__ __forceinline__ void rows() {
+    asm volatile("" : "+v"(rv));
+#pragma unroll
+    for (int j = 0; j < 2 * NL; ++j) ro[j] = __builtin_amdgcn_readlane(rv, j);
+  }
+  // tile row of pair S's even row, less pw * RB
+  static constexpr int row(int S) { return (S / (RB / 2)) * (G::PW * RB) + 2 * (S % (RB / 2)); }
+  template <int S>
+  __device__ __forceinline__ void issue() {
+    // (arithmetic, not a select of two array elements: that becomes an indexed read of the array, in scratch)
+    const size_t o = (size_t)(ro[2 * S] + hm * (ro[2 * S + 1] - ro[2 * S])) * N;
+    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(l[S]) : "v"(lab + o) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(p[S]) : "v"(per + o) : "memory");
+  }
+  __device__ __forceinline__ void wait() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    static_for<0, NL>([&](auto s) { asm volatile("" : "+v"(l[decltype(s)::value]), "+v"(p[decltype(s)::value])); });
+  }
+};
+
+// Per-stream loss coefficients of the streams a tile touches, by waves w, w + nw, ...: cf[(u - u_lo) E + e] =
+// loss_scale 2 / (S den_s), den_s summed over the stream's B rows in a fixed order (every block gets
+// bitwise-identical values; the order of csrc/hip/nmse.hip's one-pass kernel).  The tile that starts a group also
+// writes its streams' label powers (dens).
+template <int BM>
+__device__ __forceinline__ void nmse_stream_coefs(const NmseArgs& na, float* cf, int i0, int tj, int w, int nw,
+                                                  int lane) {
+  const int E = na.E, B = na.B, U = na.U, S = E * U, ub = B * E;
+  const int u_lo = i0 / ub, u_hi = (i0 + BM - 1) / ub;
+  const int nst = (u_hi - u_lo + 1) * E;
+  for (int q = w; q < nst; q += nw) {
+    const int u = u_lo + q / E, e = q % E;
+    float s = 0.f, sp = 0.f;
+    for (int b = lane; b < B; b += 64) {
+      const float2 v = na.rowden[(u * B + b) * E + e];
+      s += v.x;
+      sp += na.perf ? v.y : 0.f;
+    }
+    s = wave_sum(s);
+    sp = wave_sum(sp);
+    if (lane == 0) {
+      cf[q] = na.loss_scale * 2.f / ((float)S * s);
+      if (tj == 0 && u * ub >= i0) *reinterpret_cast<float2*>(na.dens + (e * U + u) * 2) = make_float2(s, sp);
+    }
+  }
+}
+
+// Row error partials (rsum) -> per (chunk of 16 samples, e) sums in a fixed order: part (M / CR, gx, E, 2).  fast: rsum
+// holds per (chunk, wave, expert) sums of nwb waves, else one entry per tile row.
+template <int BM, int NT>
+__device__ __forceinline__ void nmse_write_part(const NmseArgs& na, const float2* rsum, bool fast, int nwb, int i0,
+                                                int tj, int tiles_j, int tid) {
+  const int E = na.E, CR = 16 * E;
+  for (int sl = tid; sl < (BM / CR) * E; sl += NT) {
+    const int c = sl / E, e = sl % E;
+    float2 o = make_float2(0.f, 0.f);
+    if (fast) {
+      for (int w = 0; w < nwb; ++w) {
+        const float2 v = rsum[(c * nwb + w) * 3 + e];
+        o.x += v.x;
+        o.y += v.y;
+      }
+    } else {
+      for (int b = 0; b < 16; ++b) {
+        const float2 v = rsum[c * CR + b * E + e];
+        o.x += v.x;
+        o.y += v.y;
+      }
+    }
+    *reinterpret_cast<float2*>(na.part + (((size_t)((i0 + c * CR) / CR) * tiles_j + tj) * E + e) * 2) = o;
+  }
+}
+
+// The loss's row pass on a Geo::PFQ tile, run by producer pw from its prefetched rows once the fp32 tile is in LDS
+// (ct) and the coefficients in cf.  Per row: y = bf16(acc + bias) -- the value the plain forward stores and the
+// one-pass NMSE kernel reads back, so dY = bf16(coef (y - label)) is bit-identical to that pair of launches -- then
+// the error sums, and d = y - label written back over the tile with the row's coefficient beside it (crow): the
+// bias gradient's partials are summed from those by gemm_kernel in the NMSE kernel's order.
+// Error sums: with 3 experts row q of a batch is expert q % 3, so pair i of a lane (row 2 i + hi) goes to slot
+// i % 3 = expert (2 (i % 3) + hi) % 3; the slots are renamed per half-wave and reduced once per batch, side by side
+// (the FAST path of the compute waves' row pass below).  Else every row's sums cross its half-wave on their own.
+template <class G, bool FAST>
+__device__ __forceinline__ void nmse_rows_prefetched(const Args& a, NmsePrefetch<G>& pf, float* ct, const float* cf,
+                                                     int i0, int j0, int pw, int lane) {
+  using PF = NmsePrefetch<G>;
+  constexpr int PITCH = G::PITCH, RB = PF::RB, NB = PF::NB, NL = PF::NL;
+  const NmseArgs& na = a.na;
+  const int N = a.J, E = na.E, ub = na.B * E, u_lo = i0 / ub;
+  float2* rsum = reinterpret_cast<float2*>(ct + G::BM * PITCH);
+  float* crow = ct + G::BM * PITCH + 512;
+  const int c4 = (lane & 31) * 4;
+  const bool hi = pf.hi, first = (lane & 31) == 0;
+  float bv[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) bv[k] = a.bias ? bf16_to_f32(a.bias[j0 + c4 + k]) : 0.f;
+  // coefficient slot of every row of this wave (wave-uniform; a batch crosses at most one group boundary: ub >= 16)
+  int ci[2 * NL];
+#pragma unroll
+  for (int it = 0; it < NB; ++it) {
+    const int rb0 = i0 + pw * RB + it * (G::PW * RB);
+    const int ug = rb0 / ub;
+    int rem = rb0 - ug * ub, e = rem % E, g = (ug - u_lo) * E;
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      ci[it * RB + q] = g + e;
+      if (++e == E) e = 0;
+      if (++rem == ub) {
+        rem = 0;
+        g += E;
+      }
+    }
+  }
+  // (FAST: 3 experts -- i0, pw RB and the batch stride are multiples of 3)
+  float sl[NB][3][2];
+#pragma unroll
+  for (int it = 0; it < NB; ++it)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) sl[it][j][0] = sl[it][j][1] = 0.f;
+  static_for<0, NB>([&](auto it_) {
+    constexpr int it = decltype(it_)::value, NP = RB / 2;
+    // a batch's LDS reads first (issued back to back: one latency per batch, not per row pair)
+    float4 y4[NP];
+    float cfv[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const int S = it * NP + i;
+      y4[i] = *reinterpret_cast<const float4*>(ct + (pw * RB + PF::row(S) + pf.hm) * PITCH + c4);
+      cfv[i] = cf[ci[2 * S] + pf.hm * (ci[2 * S + 1] - ci[2 * S])];
+    }
+    static_for<0, NP>([&](auto i_) {
+      constexpr int i = decltype(i_)::value, S = it * NP + i;
+      const int rl = pw * RB + PF::row(S) + pf.hm;
+      const int row = i0 + rl;
+      const float coef = cfv[i];
+      const float yv[4] = {y4[i].x, y4[i].y, y4[i].z, y4[i].w};
+      float d[4], se = 0.f, sp = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float yb = bf16_to_f32(f32_to_bf16(yv[k] + bv[k]));
+        d[k] = yb - pf.l[S][k];
+        se += d[k] * d[k];
+        const float dp = yb - pf.p[S][k];
+        sp += dp * dp;
+      }
+      sp = na.perf ? sp : 0.f;
+      uint2 w;
+      w.x = (uint32_t)f32_to_bf16(coef * d[0]) | ((uint32_t)f32_to_bf16(coef * d[1]) << 16);
+      w.y = (uint32_t)f32_to_bf16(coef * d[2]) | ((uint32_t)f32_to_bf16(coef * d[3]) << 16);
+      *reinterpret_cast<uint2*>(na.dY + (size_t)row * N + j0 + c4) = w;
+      *reinterpret_cast<float4*>(ct + rl * PITCH + c4) = make_float4(d[0], d[1], d[2], d[3]);
+      if (first) crow[rl] = coef;
+      if constexpr (FAST) {
+        sl[it][i % 3][0] += se;
+        sl[it][i % 3][1] += sp;
+      } else {
+#pragma unroll
+        for (int m = 16; m >= 1; m >>= 1) {
+          se += __shfl_xor(se, m);
+          sp += __shfl_xor(sp, m);
+        }
+        if (first) rsum[rl] = make_float2(se, sp);
+      }
+    });
+  });
+  if constexpr (FAST) {
+    float pe[NB][3][2];
+#pragma unroll
+    for (int it = 0; it < NB; ++it)
+#pragma unroll
+      for (int e3 = 0; e3 < 3; ++e3)
+#pragma unroll
+        for (int k = 0; k < 2; ++k) pe[it][e3][k] = hi ? sl[it][(2 * e3 + 1) % 3][k] : sl[it][(2 * e3) % 3][k];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1)
+#pragma unroll
+      for (int it = 0; it < NB; ++it)
+#pragma unroll
+        for (int e3 = 0; e3 < 3; ++e3) {
+          pe[it][e3][0] += __shfl_xor(pe[it][e3][0], m);
+          pe[it][e3][1] += __shfl_xor(pe[it][e3][1], m);
+        }
+    if (lane == 0)   // (batch it of every producer = chunk it of the tile)
+#pragma unroll
+      for (int it = 0; it < NB; ++it)
+#pragma unroll
+        for (int e3 = 0; e3 < 3; ++e3) rsum[(it * G::PW + pw) * 3 + e3] = make_float2(pe[it][e3][0], pe[it][e3][1]);
+  }
+}
 
 // Direct-A K loop (G::ADIR): B through the 3-stage global_load_lds ring as in the staged loop, A straight into
 // registers: wave wm owns A rows wm * 16 MF .. (its MF fragments); fragment f of sub-step s of K step t is lane
@@ -670,29 +915,69 @@ __global__ void __launch_bounds__(G::NT, 1) gemm_kernel(Args a) {
   const int i0 = ti * G::BM, j0 = tj * G::BN;
   const int fr = lane & 15, fq = lane >> 4;
 
+  // PF: the loss epilogue with its rows prefetched by the producer waves (NmsePrefetch), which then stay for the
+  // epilogue.  Barriers per role, all 8 waves at each:
+  //   compute waves   prologue 1 | K steps nk - 1 | E1 ring done | E2 accumulators dumped | E3 row pass done
+  //   producer waves  prologue 1 | K steps nk - 1 | E1           | E2                     | E3
+  // The K loop's counts are those of every producer-wave tile (the producer loop below mirrors the compute waves'
+  // schedule); E1-E3 are ONE program text that both roles run, with role-specific work only between barriers.
+  constexpr bool PF = G::PFQ && EPI == EPI_NMSE;
+  const bool producer = G::PW > 0 && wave >= G::NW;
+  [[maybe_unused]] const int pw = __builtin_amdgcn_readfirstlane(wave - G::NW);
+  [[maybe_unused]] std::conditional_t<PF, NmsePrefetch<G>, NoPrefetch> pf;
+
   f32x4 acc[G::MF][G::NJ];
+  if constexpr (!PF) {
 #pragma unroll
-  for (int i = 0; i < G::MF; ++i)
+    for (int i = 0; i < G::MF; ++i)
 #pragma unroll
-    for (int j = 0; j < G::NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < G::NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
 
   const int nk = a.K / BK;
   constexpr int NS = G::NSTAGE;
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   Stager<G> stg;
   if constexpr (G::PW > 0) {
-    if (wave >= G::NW) {
+    if (producer) {
       // producer wave: the compute waves' barrier schedule (one in the prologue, one per K step but the last),
       // each barrier preceded by the wait that publishes the tile the compute waves read next; then it ends (an
       // ended wave no longer counts at a workgroup barrier, so the epilogue's barriers are the compute waves')
-      stg.init(a.P, a.ldp, a.Q, a.ldq, i0, j0, __builtin_amdgcn_readfirstlane(wave - G::NW), lane, a.pexp, a.pe);
+      // -- unless PF
+      if constexpr (PF) pf.init(a.na, i0, j0, a.J, pw, lane);
+      stg.init(a.P, a.ldp, a.Q, a.ldq, i0, j0, pw, lane, a.pexp, a.pe);
       for (int t = 0; t < NS - 1 && t < nk; ++t) stg.issue(smem + t * G::STAGE);
       vm_wait<G>((NS - 1 < nk ? NS - 1 : nk) - 1);
       __builtin_amdgcn_s_barrier();
+      if constexpr (PF) pf.rows();
       // (the KS = 1 loop has nk - 1 K-step barriers, the one-fragment-set-per-step loop nk: the waits publish
       // tile t + 1 before barrier t either way)
       const int steps = G::STEP_LOOP ? nk : nk - 1;
       int t = 0;
+      [[maybe_unused]] int npf = 0;
+      if constexpr (PF) {
+        // The first NL steady-state steps each issue Q prefetch loads after their ring tile.  vmcnt counts every
+        // load of the wave and loads retire in order, so a wait that publishes tile t + 1 may leave in flight
+        // exactly what was issued after it: tile t + 2 (NPER) and the prefetch loads of steps t - 2 and t - 1
+        // (issue order ... T(t+1) Q(t-2) T(t+2) Q(t-1) | wait of step t), i.e. NPER + Q min(t, 2).  The steps are
+        // unrolled (a register per load); a K loop shorter than NL + NS - 1 steps runs fewer of them (npf) and the
+        // rest of the prefetch is issued after the loop.  Every later wait keeps its plain count: with prefetch
+        // loads among the youngest it publishes more than it must, never less.
+        using P = NmsePrefetch<G>;
+        static_assert(NS == 4, "allowed-in-flight counts below: one tile behind the published one");
+        const int nsteady = nk - (NS - 1);
+        npf = nsteady < 0 ? 0 : nsteady < P::NL ? nsteady : P::NL;
+        static_for<0, P::NL>([&](auto s_) {
+          constexpr int s = decltype(s_)::value;
+          if (s < npf) {
+            vm_wait_n<G::NPER + P::Q * (s < 2 ? s : 2)>();
+            __builtin_amdgcn_s_barrier();
+            stg.issue(smem + ((s + NS - 1) % NS) * G::STAGE);
+            pf.template issue<s>();
+          }
+        });
+        t = npf;
+      }
       for (; t < nk - (NS - 1); ++t) {
         vm_wait<G>(NS - 3 < 0 ? 0 : NS - 3);
         __builtin_amdgcn_s_barrier();
@@ -702,78 +987,96 @@ __global__ void __launch_bounds__(G::NT, 1) gemm_kernel(Args a) {
         vm_wait<G>(nk - 2 - t);
         __builtin_amdgcn_s_barrier();
       }
-      return;
+      if constexpr (PF) {
+        static_for<0, NmsePrefetch<G>::NL>([&](auto s_) {
+          constexpr int s = decltype(s_)::value;
+          if (s >= npf) pf.template issue<s>();
+        });
+        // (the compute waves are in their last K step: the coefficients go past the ring)
+        nmse_stream_coefs<G::BM>(a.na, reinterpret_cast<float*>(smem + G::CF_OFF), i0, tj, pw, G::PW, lane);
+        pf.wait();
+      } else {
+        return;
+      }
     }
   } else {
     stg.init(a.P, a.ldp, a.Q, a.ldq, i0, j0, __builtin_amdgcn_readfirstlane(wave), lane, a.pexp, a.pe);
   }
-  Readers<G> rd;
-  rd.ra.init(0, wm * G::MF * 16, fr, fq);
-  rd.rb.init(G::A_BYTES, wn * G::NJ * 16, fr, fq);
-  // prologue: tiles 0 .. NS-2 in flight; wait for tile 0; its first fragments (the direct-A loop has its own)
-  if constexpr (!G::ADIR) {
-    if constexpr (G::PW == 0) {
-      for (int t = 0; t < NS - 1 && t < nk; ++t) stg.issue(smem + t * G::STAGE);
-      vm_wait<G>((NS - 1 < nk ? NS - 1 : nk) - 1);
+  if (!PF || !producer) {
+    if constexpr (PF) {
+#pragma unroll
+      for (int i = 0; i < G::MF; ++i)
+#pragma unroll
+        for (int j = 0; j < G::NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    __builtin_amdgcn_s_barrier();
-  }
-  Frags<G> f0, f1;
-  if constexpr (G::ADIR) {
-    da_loop<G>(acc, a, rd, stg, smem, lds0, i0, wm, fr, fq, nk);
-  } else if constexpr (!G::STEP_LOOP) {
-    rd.read_b(f0, lds0, 0);
-    rd.read_a(f0, lds0, 0);
+    Readers<G> rd;
+    rd.ra.init(0, wm * G::MF * 16, fr, fq);
+    rd.rb.init(G::A_BYTES, wn * G::NJ * 16, fr, fq);
+    // prologue: tiles 0 .. NS-2 in flight; wait for tile 0; its first fragments (the direct-A loop has its own)
+    if constexpr (!G::ADIR) {
+      if constexpr (G::PW == 0) {
+        for (int t = 0; t < NS - 1 && t < nk; ++t) stg.issue(smem + t * G::STAGE);
+        vm_wait<G>((NS - 1 < nk ? NS - 1 : nk) - 1);
+      }
+      __builtin_amdgcn_s_barrier();
+    }
+    Frags<G> f0, f1;
+    if constexpr (G::ADIR) {
+      da_loop<G>(acc, a, rd, stg, smem, lds0, i0, wm, fr, fq, nk);
+    } else if constexpr (!G::STEP_LOOP) {
+      rd.read_b(f0, lds0, 0);
+      rd.read_a(f0, lds0, 0);
 
-    // Each K step t: MFMAs of sub-step 0 of tile t with sub-step 1's reads woven in; wait for tile t+1
-    // (counted vmcnt) + barrier; refill the stage tile t-1 used; MFMAs of sub-step 1 with tile t+1's
-    // sub-step-0 reads woven in.  Steady-state steps (refill always, a constant wait) form a loop with no
-    // branch inside; the last NS-1 steps are peeled (no refill, shrinking waits).
-    auto step = [&](int t, auto refill, int ahead) {
-      const uint32_t cur = lds0 + (t % NS) * G::STAGE, nxt = lds0 + ((t + 1) % NS) * G::STAGE;
-      rd.template mma_read<true>(acc, f0, f1, cur, 1);
-      if constexpr (G::DBG != 1 && G::PW == 0) vm_wait<G>(ahead);
-      __builtin_amdgcn_s_barrier();
-      if constexpr (decltype(refill)::value && G::DBG != 1 && G::PW == 0)
-        stg.issue(smem + ((t + NS - 1) % NS) * G::STAGE);
-      __builtin_amdgcn_sched_barrier(0);
-      rd.template mma_read<true>(acc, f1, f0, nxt, 0);
-    };
-    int t = 0;
-    for (; t < nk - (NS - 1); ++t) step(t, std::true_type{}, NS - 3 < 0 ? 0 : NS - 3);
-    for (; t < nk - 1; ++t) step(t, std::false_type{}, nk - 2 - t);
-    rd.template mma_read<true>(acc, f0, f1, lds0 + (t % NS) * G::STAGE, 1);
-    rd.template mma_read<false>(acc, f1, f0, 0, 0);
-  } else {
-    // KS = 2: this wave's sub-step sk of every tile.  Step t: wait for tile t+1 + barrier; refill the
-    // stage of tile t-1 (every wave finished reading it during step t-1); the MFMAs of tile t with tile
-    // t+1's fragments read in between.  Two steps per loop iteration keep the fragment sets static.
-    // (the wave's sub-step becomes sub-step 0 of its readers: a runtime index into base[] would put the
-    // readers in scratch -- guide §5.4 rule 20)
-    if constexpr (G::KS == 2) {
-      rd.ra.base[0] = wk ? rd.ra.base[1] : rd.ra.base[0];
-      rd.rb.base[0] = wk ? rd.rb.base[1] : rd.rb.base[0];
-    }
-    constexpr int sk = 0;
-    rd.read_b(f0, lds0, sk);
-    rd.read_a(f0, lds0, sk);
-    auto step = [&](int t, Frags<G>& cur, Frags<G>& nxt) __attribute__((always_inline)) {
-      const int ahead = nk - 2 - t < NS - 3 ? nk - 2 - t : NS - 3;
-      if constexpr (G::DBG != 1 && G::PW == 0) vm_wait<G>(ahead);
-      __builtin_amdgcn_s_barrier();
-      if (G::DBG != 1 && G::PW == 0 && t + NS - 1 < nk) stg.issue(smem + ((t + NS - 1) % NS) * G::STAGE);
-      __builtin_amdgcn_sched_barrier(0);
-      rd.template mma_read<true>(acc, cur, nxt, lds0 + ((t + 1) % NS) * G::STAGE, sk);
-    };
-    // (nk even: checked by the launcher)
-    int t = 0;
-    for (; t < nk - 2; t += 2) {
+      // Each K step t: MFMAs of sub-step 0 of tile t with sub-step 1's reads woven in; wait for tile t+1
+      // (counted vmcnt) + barrier; refill the stage tile t-1 used; MFMAs of sub-step 1 with tile t+1's
+      // sub-step-0 reads woven in.  Steady-state steps (refill always, a constant wait) form a loop with no
+      // branch inside; the last NS-1 steps are peeled (no refill, shrinking waits).
+      auto step = [&](int t, auto refill, int ahead) {
+        const uint32_t cur = lds0 + (t % NS) * G::STAGE, nxt = lds0 + ((t + 1) % NS) * G::STAGE;
+        rd.template mma_read<true>(acc, f0, f1, cur, 1);
+        if constexpr (G::DBG != 1 && G::PW == 0) vm_wait<G>(ahead);
+        __builtin_amdgcn_s_barrier();
+        if constexpr (decltype(refill)::value && G::DBG != 1 && G::PW == 0)
+          stg.issue(smem + ((t + NS - 1) % NS) * G::STAGE);
+        __builtin_amdgcn_sched_barrier(0);
+        rd.template mma_read<true>(acc, f1, f0, nxt, 0);
+      };
+      int t = 0;
+      for (; t < nk - (NS - 1); ++t) step(t, std::true_type{}, NS - 3 < 0 ? 0 : NS - 3);
+      for (; t < nk - 1; ++t) step(t, std::false_type{}, nk - 2 - t);
+      rd.template mma_read<true>(acc, f0, f1, lds0 + (t % NS) * G::STAGE, 1);
+      rd.template mma_read<false>(acc, f1, f0, 0, 0);
+    } else {
+      // KS = 2: this wave's sub-step sk of every tile.  Step t: wait for tile t+1 + barrier; refill the
+      // stage of tile t-1 (every wave finished reading it during step t-1); the MFMAs of tile t with tile
+      // t+1's fragments read in between.  Two steps per loop iteration keep the fragment sets static.
+      // (the wave's sub-step becomes sub-step 0 of its readers: a runtime index into base[] would put the
+      // readers in scratch -- guide §5.4 rule 20)
+      if constexpr (G::KS == 2) {
+        rd.ra.base[0] = wk ? rd.ra.base[1] : rd.ra.base[0];
+        rd.rb.base[0] = wk ? rd.rb.base[1] : rd.rb.base[0];
+      }
+      constexpr int sk = 0;
+      rd.read_b(f0, lds0, sk);
+      rd.read_a(f0, lds0, sk);
+      auto step = [&](int t, Frags<G>& cur, Frags<G>& nxt) __attribute__((always_inline)) {
+        const int ahead = nk - 2 - t < NS - 3 ? nk - 2 - t : NS - 3;
+        if constexpr (G::DBG != 1 && G::PW == 0) vm_wait<G>(ahead);
+        __builtin_amdgcn_s_barrier();
+        if (G::DBG != 1 && G::PW == 0 && t + NS - 1 < nk) stg.issue(smem + ((t + NS - 1) % NS) * G::STAGE);
+        __builtin_amdgcn_sched_barrier(0);
+        rd.template mma_read<true>(acc, cur, nxt, lds0 + ((t + 1) % NS) * G::STAGE, sk);
+      };
+      // (nk even: checked by the launcher)
+      int t = 0;
+      for (; t < nk - 2; t += 2) {
+        step(t, f0, f1);
+        step(t + 1, f1, f0);
+      }
       step(t, f0, f1);
-      step(t + 1, f1, f0);
+      rd.template mma_read<false>(acc, f1, f0, 0, 0);
     }
-    step(t, f0, f1);
-    rd.template mma_read<false>(acc, f1, f0, 0, 0);
-  }
+  }   // (compute waves)
 
   // ---------------------------------------------------------------- epilogue
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -886,28 +1189,41 @@ __global__ void __launch_bounds__(G::NT, 1) gemm_kernel(Args a) {
     // stream's B rows in a fixed order: every block gets bitwise-identical values)
     const NmseArgs& na = a.na;
     const int N = a.J;
+    if constexpr (PF) {
+      // (E2 is behind us: the fp32 tile is in LDS, the coefficients past the ring since E1)
+      const float* cf = reinterpret_cast<const float*>(smem + G::CF_OFF);
+      if (producer) {
+        if (na.E == 3) nmse_rows_prefetched<G, true>(a, pf, ct, cf, i0, j0, pw, lane);
+        else nmse_rows_prefetched<G, false>(a, pf, ct, cf, i0, j0, pw, lane);
+      }
+      __syncthreads();   // E3
+      const float2* rsum = reinterpret_cast<const float2*>(ct + G::BM * PITCH);
+      const float* crow = ct + G::BM * PITCH + 512;
+      nmse_write_part<G::BM, G::NT>(na, rsum, na.E == 3, G::PW, i0, tj, tiles_j, tid);
+      // The bias gradient's partials, bit-identical to the one-pass NMSE kernel's: per chunk of 4 E rows (its row
+      // chunks; the tile starts on one) and column, acc = fma(coef, y - label, acc) over the rows in order -- the
+      // contraction that kernel is compiled to -- from the d and coef the row pass left in LDS.  colsum (M / 4E, N).
+      auto colsums = [&](auto cs_) __attribute__((always_inline)) {   // (a constant chunk: the LDS reads up front)
+        const int CS = decltype(cs_)::value ? decltype(cs_)::value : 4 * na.E;
+        for (int it = tid; it < (G::BM / CS) * G::BN; it += G::NT) {
+          const int ch = it / G::BN, j = it % G::BN;
+          float s = 0.f;
+#pragma unroll
+          for (int q = 0; q < CS; ++q) s = __builtin_fmaf(crow[ch * CS + q], ct[(ch * CS + q) * PITCH + j], s);
+          na.colsum[(size_t)(i0 / CS + ch) * N + j0 + j] = s;
+        }
+      };
+      if (na.E == 3) colsums(std::integral_constant<int, 12>{});
+      else colsums(std::integral_constant<int, 0>{});
+      return;
+    }
     float* red = ct + G::BM * PITCH;                  // 64 floats after the tile
     const float bv0 = a.bias ? bf16_to_f32(a.bias[j0 + c0]) : 0.f;
     const float bv1 = a.bias ? bf16_to_f32(a.bias[j0 + c0 + 1]) : 0.f;
-    const int E = na.E, B = na.B, U = na.U, S = E * U;
+    const int E = na.E, B = na.B;
     const int ub = B * E;
-    const int u_lo = i0 / ub, u_hi = (i0 + G::BM - 1) / ub;
-    const int nst = (u_hi - u_lo + 1) * E;
-    for (int q = wave; q < nst; q += G::NW) {
-      const int u = u_lo + q / E, e = q % E;
-      float s = 0.f, sp = 0.f;
-      for (int b = lane; b < B; b += 64) {
-        const float2 v = na.rowden[(u * B + b) * E + e];
-        s += v.x;
-        sp += na.perf ? v.y : 0.f;
-      }
-      s = wave_sum(s);
-      sp = wave_sum(sp);
-      if (lane == 0) {
-        red[q] = na.loss_scale * 2.f / ((float)S * s);
-        if (tj == 0 && u * ub >= i0) *reinterpret_cast<float2*>(na.dens + (e * U + u) * 2) = make_float2(s, sp);
-      }
-    }
+    const int u_lo = i0 / ub;
+    nmse_stream_coefs<G::BM>(na, red, i0, tj, wave, G::NW, lane);
     __syncthreads();
     float2* rsum = reinterpret_cast<float2*>(red + 64 + G::NW * 128);   // per-row (err^2, errperf^2)
     float cs0 = 0.f, cs1 = 0.f;
@@ -1023,26 +1339,7 @@ __global__ void __launch_bounds__(G::NT, 1) gemm_kernel(Args a) {
         na.amax8[blockIdx.x] = fmaxf(na.amax8[blockIdx.x], b);
       }
     }
-    // row error partials -> per (chunk of 16 samples, e) sums in a fixed order: part (M / CR, gx, E, 2)
-    const int CR = 16 * E;
-    for (int sl = tid; sl < (G::BM / CR) * E; sl += G::NT) {
-      const int c = sl / E, e = sl % E;
-      float2 o = make_float2(0.f, 0.f);
-      if (fast) {
-        for (int w = 0; w < G::NW; ++w) {
-          const float2 v = rsum[(c * G::NW + w) * 3 + e];
-          o.x += v.x;
-          o.y += v.y;
-        }
-      } else {
-        for (int b = 0; b < 16; ++b) {
-          const float2 v = rsum[c * CR + b * E + e];
-          o.x += v.x;
-          o.y += v.y;
-        }
-      }
-      *reinterpret_cast<float2*>(na.part + (((size_t)((i0 + c * CR) / CR) * tiles_j + tj) * E + e) * 2) = o;
-    }
+    nmse_write_part<G::BM, G::NT>(na, rsum, fast, G::NW, i0, tj, tiles_j, tid);
     float2* cpart = reinterpret_cast<float2*>(red + 64);
     cpart[wave * 64 + lane] = make_float2(cs0, cs1);
     __syncthreads();
@@ -1142,6 +1439,10 @@ QD_API int qd_gemm_tile_m(int cfg) {
                                                                                                       : FwdA::BM;
 }
 
+// Rows per colsum partial row of qd_gemm_fwd_nmse (bf16): the tile's, but 4 E on the tile whose producers run the
+// row pass (cfg 8) -- the one-pass NMSE kernel's row chunks, for a bit-identical bias gradient
+QD_API int qd_gemm_nmse_colsum_rows(int cfg, int E) { return cfg == 8 && FwdQ::PFQ ? 4 * E : qd_gemm_tile_m(cfg); }
+
 QD_API int qd_gemm_fwd_ok(int M, int N, int K, int cfg) {
   if (K % BK || N % 128) return 0;
   if (cfg == 101 || cfg == 102) return M % FwdA::BM == 0;
@@ -1178,8 +1479,10 @@ QD_API int qd_gemm_fwd_bias(const uint16_t* A, const uint16_t* W, const uint16_t
 }
 
 // The training forward with the HDCE-loss epilogue (see the header).  rows M = U*B*E in (u, b, e)
-// order, B % 16 == 0; part (M / 16E, N / 128, E, 2), colsum (M / tile_m, N), dens (S, 2) -- then
-// qd_nmse_finish (chunks = M / tile_m, gx = N / 128, chunks_per_u = B / 16) or a deferred LossFinish.
+// order, B % 16 == 0; part (M / 16E, N / 128, E, 2), colsum (M / cr, N) with cr = qd_gemm_nmse_colsum_rows,
+// dens (S, 2) -- then qd_nmse_finish (chunks = M / cr, gx = N / 128, chunks_per_u = B / 16) or a deferred
+// LossFinish.  cfg 8: the producer waves prefetch the label rows and run the row pass (NmsePrefetch); its dY and
+// colsum are bit-identical to qd_gemm_fwd_bias (cfg 8) + qd_nmse_fused (rpc = 4 E) on the same inputs.
 QD_API int qd_gemm_fwd_nmse(const uint16_t* A, const uint16_t* W, const uint16_t* bias, const float* label,
                             const float* perf, const int* rowoff, const float* rowden, uint16_t* dY, float* part,
                             float* colsum, float* dens, int M, int N, int K, int E, int U, int B, float loss_scale,
@@ -1194,7 +1497,7 @@ QD_API int qd_gemm_fwd_nmse(const uint16_t* A, const uint16_t* W, const uint16_t
   if (cfg == 1) return launch<FwdB, EPI_NMSE, 1, 4>(a, st);
   if (cfg == 6) return launch<FwdB4, EPI_NMSE, 1, 4>(a, st);
   if (cfg == 7) return launch<FwdP, EPI_NMSE, 1, 4>(a, st);
-  if (cfg == 8) return launch<FwdQ, EPI_NMSE, 4, 8>(a, st);
+  if (cfg == 8) return FwdQ::BM % (4 * E) ? (int)hipErrorInvalidValue : launch<FwdQ, EPI_NMSE, 4, 8>(a, st);
   if (cfg == 9) return launch<FwdP3, EPI_NMSE, 1, 4>(a, st);
   if (cfg == 10) return launch<FwdR, EPI_NMSE, 1, 4>(a, st);
   if (cfg == 3) return launch<FwdD, EPI_NMSE, 1, 4>(a, st);

@@ -17,13 +17,18 @@ class Knobs:
     # (csrc/hip/gemm.hip; the rest on hipBLASLt), and their tile configurations (forward, wgrad, dgrad).
     # 8,7,6 (round 5) = the producer-wave tiles: isolated 33.0 / 38.8 / 35.1 us against 40.3 / 42.2 / 35.8 for round
     # 4's 6,1,2; in the step 0.3958-0.3967 against 0.3992-0.4025 ms (profiles/r5_02_gemm_probe.txt, r5_03_ab.txt)
-    # "fwd" instead of "fwdplain": the forward with the loss in its epilogue (gemm.hip EPI_NMSE) where it tiles, else
-    # the plain hand-written forward + the one-pass NMSE kernel.  Since the epilogue reduces its error sums per (batch,
-    # expert) rather than per row the two are level: 0.3721 / 0.3726 against 0.3745 / 0.3737 ms on one box, 0.3842-
-    # 0.3847 against 0.3839-0.3845 on another (profiles/r5_29_nmse_epilogue_ab.txt, r5_42_fused_fwd_ab.txt) -- the
-    # plain forward stays.  (Shapes the epilogue does not tile fell back to hipBLASLt, whose forward breaks the
-    # split-forward plans' equality with the serial step: profiles/r5_32_*, r5_41_map.txt, r5_42_library_fwd.log)
-    hand_gemm: str = "fwdplain,wgrad,dgrad"
+    # "fwd": the forward with the loss in its epilogue (gemm.hip EPI_NMSE) where it tiles, else the plain hand-written
+    # forward ("fwdplain") + the one-pass NMSE kernel.  History: with the compute waves loading the label rows after
+    # the K loop the two were level -- 0.3721 / 0.3726 against 0.3745 / 0.3737 ms on one box, 0.3842-0.3847 against
+    # 0.3839-0.3845 on another (profiles/r5_29_nmse_epilogue_ab.txt, r5_42_fused_fwd_ab.txt) -- and the plain forward
+    # shipped.  Since the cfg-8 tile's producer waves prefetch those rows during the K loop and run the row pass
+    # (gemm.hip NmsePrefetch; dY and the bias partials bit-identical to the two-launch path) the fused forward is
+    # faster: 0.3606-0.3655 against 0.3736-0.3745 ms, 0.3683-0.3708 against 0.3798-0.3815 on a second box (three
+    # alternating rounds each) and 0.3548-0.3563 against 0.3590-0.3591 on a third (profiles/r8_fwd_prefetch_ab.txt);
+    # the NMSE launch leaves the step.
+    # (Shapes the epilogue does not tile once fell back to hipBLASLt, whose forward breaks the split-forward plans'
+    # equality with the serial step: profiles/r5_32_*, r5_41_map.txt, r5_42_library_fwd.log)
+    hand_gemm: str = "fwd,wgrad,dgrad"
     gemm_cfg: str = "8,7,6"
     # fp8 estimator: the hand-written e4m3 forward (else torch._scaled_mm + the NMSE kernel), e4m3 FC gradients
     hand_fp8: bool = True

@@ -265,7 +265,9 @@ class StreamNMSE:
         self._check_labels(label)
         if perf is not None:
             self._check_labels(perf)
-        tm = gemm_tile_m(cfg)
+        # rows per bias-gradient partial row: the GEMM's tile, or (bf16 cfg 8, whose producer waves run the loss) the
+        # one-pass NMSE kernel's 4 E row chunks -- that forward's dY and partials are bit-identical to ``fused``'s
+        tm = gemm_tile_m(cfg) if f8 else int(nat.fn(nat.hip_lib(), "qd_gemm_nmse_colsum_rows", [_i, _i])(cfg, E))
         gx = N // 128
         dev = A.device
         if getattr(self, "_gz", None) is None or self._gz[0] != (tm, N):

@@ -298,8 +298,9 @@ class HDCEStep:
         self.stage_hook = None  # optional callable(stage) between forward launches (stream forks)
         # the FC GEMMs: hand-written MFMA kernels (csrc/hip/gemm.hip; knobs.KNOBS.hand_gemm = "": hipBLASLt) and
         # their tile configurations (forward, wgrad, dgrad; knobs.KNOBS.gemm_cfg).  Default: all three hand-written,
-        # round 5: the producer-wave tiles (cfg 8, 7, 6) and the forward with the loss in its epilogue ("fwd", see
-        # knobs.py); the round-4 notes below are the history of that choice --
+        # round 5: the producer-wave tiles (cfg 8, 7, 6); the forward with the loss in its epilogue ("fwd") since its
+        # producer waves prefetch the label rows (gemm.hip NmsePrefetch; knobs.py has the measurements -- before that
+        # it was level with "fwdplain" + the NMSE kernel, which shipped); the round-4 notes below are the history --
         #   forward  "fwdplain", cfg 6: 192 x 128 tiles on a 4-stage LDS ring (round 4: two tiles in flight behind
         #            the MFMAs; isolated 43.5 vs 50.2 us for the 3-stage cfg 1, in the step 0.4012 / 0.3999 vs
         #            0.4070 / 0.4068 ms, profiles/r4_16_*); 192 workgroups, so ~64 CUs stay free for the concurrent
@@ -504,7 +505,8 @@ class HDCEStep:
         N = m.fc_w.shape[0]
         c = self.gemm_cfg
         tm = gemm_tile_m(c[0])
-        return (gemm_fwd_ok(M, N, K, c[0]) and N % 256 == 0 and M % 128 == 0 and K % 256 == 0
+        # (M % 64: the weight gradient's K step -- _wgrad and dgrad check their own tilings)
+        return (gemm_fwd_ok(M, N, K, c[0]) and N % 256 == 0 and M % 64 == 0 and K % 256 == 0
                 and (tm // (self.B * m.E) + 2) * m.E <= 64 and self.B % 16 == 0 and tm % (16 * m.E) == 0)
 
     @torch.no_grad()
