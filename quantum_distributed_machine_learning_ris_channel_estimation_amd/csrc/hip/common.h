@@ -57,10 +57,20 @@ __device__ __forceinline__ unsigned long long phase_stamp() {
 // the same thing.  Explicit: bitwise the same values in every kernel.
 //   gate  : the ReLU passed, a z + b > 0 (fma)           xhat : (z - mean) * invstd
 //   dz    : c1 g - c2 - c3 xhat                           red  : s1 += g, s2 += g xhat (fma)
+// __fmul_rn / __fsub_rn alone do not pin a rounding: this toolchain's headers define them as plain `*` / `-`, which
+// -ffp-contract=fast still fuses where it likes (fma(c1, g, -c2) is one fp32 ulp -- now and then one bf16 dz -- away
+// from the rounded product; tests/test_conv_exact_gpu.py holds every kernel to the unfused value).  A product that
+// must be rounded before the addition consuming it goes through rounded_product: opaque to the compiler, no
+// instruction emitted.
+__device__ __forceinline__ float rounded_product(float a, float b) {
+  float p = a * b;
+  asm("" : "+v"(p));
+  return p;
+}
 __device__ __forceinline__ bool bn_gate(float a, float z, float b) { return __fmaf_rn(a, z, b) > 0.f; }
 __device__ __forceinline__ float bn_xhat(float z, float mu, float inv) { return __fmul_rn(__fsub_rn(z, mu), inv); }
 __device__ __forceinline__ float bn_dz(float g, float xh, float c1, float c2, float c3) {
-  return __fsub_rn(__fsub_rn(__fmul_rn(c1, g), c2), __fmul_rn(c3, xh));
+  return __fsub_rn(__fsub_rn(rounded_product(c1, g), c2), rounded_product(c3, xh));
 }
 __device__ __forceinline__ void bn_red(float& s1, float& s2, float g, float xh) {
   s1 = __fadd_rn(s1, g);
