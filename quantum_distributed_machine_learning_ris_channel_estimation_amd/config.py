@@ -78,7 +78,7 @@ class RunnerConfig:
     # epoch checkpoints under the tag "swa" (0: off; the reference evaluates the last epoch's weights)
     swa_epochs: int = 0
     # on-chip QSC training (train-qsc; EvalConfig's names): the backward of the quantum layer (ops/quantum.py
-    # DIFF_METHODS: adjoint | parameter_shift | on_chip), the measurement shots per circuit (0: exact), and the
+    # DIFF_METHODS: adjoint | parameter_shift | on_chip | noisy_adjoint), the measurement shots per circuit (0: exact), and the
     # device noise the shots are measured under (needs qsc_shots > 0): Pauli error rate per fused one-qubit gate /
     # per CNOT, readout error 0 -> 1 / 1 -> 0, gate-error realisations the shots are split over.  Anything but the
     # defaults trains through the module path (no fused step, no graph capture), world size 1 only.

@@ -93,7 +93,8 @@ class QuantumLayer(nn.Module):
 
     ``noise`` (settable; None or an ``ops.quantum.NoiseModel``) and ``trajectories`` (settable; 1 .. 1024) measure
     the shots on a device with Pauli gate errors and readout error (``qsim(noise=, trajectories=)``); they need
-    ``shots``, and gradients stay those of the noiseless circuit unless ``diff_method`` is "on_chip"."""
+    ``shots``, and gradients stay those of the noiseless circuit unless ``diff_method`` is "on_chip" or
+    "noisy_adjoint" (needs ``noise`` and ``shots``: the adjoint through the error gates the forward sampled)."""
 
     def __init__(self, n_qubits: int, n_layers: int, backend: Optional[str] = None, shots: Optional[int] = None,
                  diff_method: str = "adjoint", noise=None, trajectories: int = 1):
@@ -146,8 +147,8 @@ class QSC_P128(nn.Module):
     defined there): Linear(n, n) + Tanh in place of the VQC, an equal-width classical ablation
     with the same (-1, 1) output range as <Z_i>.
     ``shots`` goes to the ``qlayer`` (finite-shot <Z_i>; None = exact), and so does ``diff_method``
-    ("adjoint", "parameter_shift": the gradient an on-chip QNN measures, or "on_chip": that gradient measured
-    under ``noise`` too), ``noise`` and ``trajectories`` (the device's gate and readout errors under which the
+    ("adjoint", "parameter_shift": the gradient an on-chip QNN measures, "on_chip": that gradient measured
+    under ``noise`` too, or "noisy_adjoint": the exact gradient through the sampled error gates), ``noise`` and ``trajectories`` (the device's gate and readout errors under which the
     shots are measured).
     """
 

@@ -33,6 +33,12 @@ on ``hip``, composed from the C++ oracles of the same integer contract on ``cpu`
 On-chip gradients (``qsim(..., shots=N, diff_method="on_chip", noise=, trajectories=T)``, ``pshift_rows(noise=)``):
 the parameter-shift rule with every shifted circuit measured on that noisy device under its own counter --
 csrc/hip/qsim_onchip.hip (n <= 12) on ``hip``, the noisy forward's host composition per circuit on ``cpu``.
+
+Noise-aware adjoint (``qsim(..., shots=N, noise=, trajectories=T, diff_method="noisy_adjoint")``,
+``noisy_adjoint_rows``): the exact gradient of the noisy forward's mean given its sampled Pauli frames -- the adjoint
+method run through every trajectory's framed circuit, what QuantumNAT's noise injection differentiates on a
+simulator; csrc/hip/qsim_nadj.hip (n <= 12) on ``hip``, the parameter-shift rule over ``qsim_probs(frames=)`` in
+fp64 on ``cpu``.
 """
 from __future__ import annotations
 
@@ -693,7 +699,7 @@ def _qsim_noisy(x, w, be, noise, shots, T, seed, counter) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------- parameter shift
-DIFF_METHODS = ("adjoint", "parameter_shift", "on_chip")
+DIFF_METHODS = ("adjoint", "parameter_shift", "on_chip", "noisy_adjoint")
 PSHIFT_ID_SHIFT = 48   # circuit (p, s) draws under call counter c + (id << 48), id = 1 + 2p + s; the forward is id 0
 
 
@@ -862,6 +868,174 @@ class _QSimPShift(torch.autograd.Function):
         return dx, dw, None, None, None, None, None, None, None
 
 
+# ----------------------------------------------------------------------------- noise-aware adjoint
+def nadj_split(trajectories: int, n: int) -> int:
+    """The workgroups per sample csrc/hip/qsim_nadj.hip launches for that many trajectories of n qubits (above 1
+    their partial rows are summed in a fixed order: the result is deterministic)."""
+    return nat.fn(nat.hip_lib(), "qd_qsim_nadj_split", [_i, _i])(int(trajectories), int(n))
+
+
+def hip_qsim_noisy_adjoint(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, G: torch.Tensor, noise: "NoiseModel",
+                           trajectories: int = 1, seed: int = 0, ctr0: int = 0, counter_ptr=None, wgroup: int = 0,
+                           Ebar: Optional[torch.Tensor] = None, frames: Optional[torch.Tensor] = None) -> None:
+    """Raw launcher of csrc/hip/qsim_nadj.hip (n <= 12): G (B, 2nL) fp32, the gradient rows of sum(gE * Ebar) with
+    Ebar the mean of the noisy shots forward given the Pauli frames it draws under (seed, counter); Ebar (nullable;
+    B, n) fp32, frames (nullable; B, T, L, 2) int32 every trajectory's frames."""
+    B, n = x.shape
+    L = w.shape[-3]
+    T = int(trajectories)
+    thr1, thr2, thr_ro = noise.thresholds(n, x.device)
+    split = nadj_split(T, n) if 2 <= n <= HIP_SHOTS_MAX_QUBITS else 0
+    work = torch.empty(split * B * (2 * n * L + n), device=x.device, dtype=torch.float32) if split > 1 else None
+    f = nat.fn(nat.hip_lib(), "qd_qsim_noisy_adjoint",
+               [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _u64, _u64, _p, _p])
+    opt = lambda t: nat.ptr(t) if t is not None else None   # noqa: E731
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(gE), nat.ptr(G), opt(Ebar), opt(frames), opt(work), nat.ptr(thr1),
+                nat.ptr(thr2), nat.ptr(thr_ro), B, n, L, wgroup, T, seed & _M64, ctr0 & _M64, counter_ptr,
+                nat.stream_ptr(x.device)), "qd_qsim_noisy_adjoint")
+
+
+def _nadj_rows_cpu(x, w, gE, noise, T, seed, ctr0):
+    """(G, Ebar) composed from the host oracles, in fp64: the frames the noisy forward draws, then the framed
+    circuit's exact <Z> of every trajectory -- for Ebar as it stands, for G with one angle shifted by +-pi/2 (the
+    shift rule is exact for a circuit with fixed Paulis inserted)."""
+    B, n = x.shape
+    L = w.shape[-3]
+    P = 2 * n * L
+    frames = pauli_frames(noise_sites(noise, B, n, L, T, seed, ctr0))
+    fr = frames.view(B * T, L, 2)
+    xr = x.repeat_interleave(T, dim=0)
+    zs = z_signs(n, dtype=torch.float64)
+    bits = (frames[:, :, L - 1, 0, None] >> torch.arange(n)) & 1          # (B, T, n): the last X mask
+    sgn = (1 - 2 * bits).double()
+    thr_ro = torch.from_numpy(noise.thresholds_host(n)[2].astype("int64"))
+    c = 1.0 - (thr_ro[:, 0] + thr_ro[:, 1]).double() / 65536.0
+    d = (thr_ro[:, 1] - thr_ro[:, 0]).double() / 65536.0
+
+    def mean_z(ws):   # (B, n): mean over the trajectories of s_j E_j
+        return ((qsim_probs(xr, ws, "cpu", frames=fr) @ zs).view(B, T, n) * sgn).mean(1)
+
+    Ebar = c * mean_z(w) + d
+    gc = gE.double() * c
+    G = torch.zeros(B, P, dtype=torch.float64)
+    for p in range(P):
+        E = []
+        for sh in (0.5 * math.pi, -0.5 * math.pi):
+            ws = w.clone()
+            ws.view(-1, P)[:, p] += sh
+            E.append(mean_z(ws))
+        G[:, p] = (gc * (E[0] - E[1]) * 0.5).sum(1)
+    return G.float(), Ebar
+
+
+@torch.no_grad()
+def noisy_adjoint_rows(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, noise: "NoiseModel", trajectories: int = 1,
+                       seed: int = 0, counter=0, backend: Optional[str] = None, return_expectation: bool = False):
+    """Per-sample noise-aware adjoint gradients G (B, 2nL) fp32 (``pshift_rows``'s layout: column p = (l n + q) 2 + k
+    is w[l, q, k]'s; dx = G[:, 0:2n:2]; dw = G summed over the samples) of sum(gE * Ebar), where, with the Pauli
+    frames the noisy forward draws for (``seed``, ``counter``) over ``trajectories`` = T,
+
+        Ebar[b, j] = c_j mean_tau s_j(tau) E_j^tau + d_j
+
+    is the mean of ``qsim(x, w, shots=, noise=, trajectories=T)`` over its outcome and readout draws: E_j^tau the
+    exact <Z_j> of trajectory tau's circuit (frames behind the rings of layers 0 .. L-2), s_j(tau) = -1 when the
+    last layer's X mask has bit j set, c_j = 1 - (thr01_j + thr10_j) / 65536 and d_j = (thr10_j - thr01_j) / 65536
+    from the model's 16-bit readout thresholds.  No shots are needed.  ``return_expectation``: (G, Ebar), Ebar
+    (B, n) fp32 on ``hip`` and fp64 on ``cpu`` (as ``qsim_probs``).  csrc/hip/qsim_nadj.hip on ``hip`` (n <= 12), the
+    fp64 composition of the host oracles on ``cpu``."""
+    _check_shapes(x, w)
+    B, n = x.shape
+    L = w.shape[-3]
+    if not isinstance(noise, NoiseModel):
+        raise ValueError(f"noise must be a NoiseModel, got {type(noise).__name__}")
+    T = int(trajectories)
+    if not 1 <= T <= MAX_TRAJECTORIES:
+        raise ValueError(f"trajectories must be in 1..{MAX_TRAJECTORIES}, got {T}")
+    _check_noise_shape(n, L)
+    be = backend if backend not in (None, "auto") else default_backend(x.device)
+    x = x.detach().float().contiguous()
+    w = w.detach().float().contiguous()
+    gE = gE.detach().float().contiguous()
+    if tuple(gE.shape) != (B, n):
+        raise ValueError(f"gE must be ({B}, {n}), got {tuple(gE.shape)}")
+    if be == "hip":
+        if x.device.type != "cuda":
+            raise RuntimeError("hip backend needs CUDA/HIP tensors")
+        _hip_shots_limit(n)
+        ctr0, cptr = _split_counter(counter, x.device)
+        G = torch.empty(B, 2 * n * L, device=x.device, dtype=torch.float32)
+        Ebar = torch.empty(B, n, device=x.device, dtype=torch.float32) if return_expectation else None
+        if B > 0:
+            hip_qsim_noisy_adjoint(x, w, gE, G, noise, T, int(seed), ctr0, cptr, wgroup_of(x, w), Ebar)
+        return (G, Ebar) if return_expectation else G
+    if be == "cpu":
+        if x.device.type != "cpu":
+            raise RuntimeError("cpu backend needs CPU tensors")
+        if n > HIP_SHOTS_MAX_QUBITS:
+            raise NotImplementedError(f"the noise model supports n <= {HIP_SHOTS_MAX_QUBITS} qubits, got {n}")
+        ctr0, _ = _split_counter(counter, x.device)
+        G, Ebar = _nadj_rows_cpu(x, w, gE, noise, T, int(seed), ctr0)
+        return (G, Ebar) if return_expectation else G
+    if be == "torch":
+        raise ValueError("the torch backend has no noise model; use hip or cpu")
+    raise ValueError(f"unknown backend {be!r}")
+
+
+class _QSimNoisyAdjoint(torch.autograd.Function):
+    """Forward: the noisy finite-shot forward, unchanged.  Backward: the adjoint through the Pauli frames that
+    forward sampled -- the same seed, counter and trajectories (a device counter is read again by the backward:
+    advance it after the backward)."""
+
+    @staticmethod
+    def forward(ctx, x, w, be, noise, shots, T, seed, counter):
+        B, n = x.shape
+        x = x.detach().float().contiguous()
+        w = w.detach().float().contiguous()
+        ctx.save_for_backward(x, w)
+        ctx.args = (be, noise, T, seed, counter)
+        ctr0, cptr = _split_counter(counter, x.device)
+        if be == "hip":
+            E = torch.empty(B, n, device=x.device, dtype=torch.float32)
+            if B > 0:
+                hip_qsim_noisy_shots_fwd(x, w, E, None, noise, shots, T, seed, ctr0, cptr, wgroup_of(x, w))
+            return E
+        return _noisy_shots_cpu(x, w, noise, shots, T, seed, ctr0)
+
+    @staticmethod
+    def backward(ctx, gE):
+        x, w = ctx.saved_tensors
+        be, noise, T, seed, counter = ctx.args
+        B, n = x.shape
+        L = w.shape[-3]
+        P = 2 * n * L
+        G = noisy_adjoint_rows(x, w, gE, noise, T, seed, counter, be)
+        dx = G[:, 0:2 * n:2].contiguous()
+        if be == "hip" and B > 0:   # deterministic: no float atomics
+            dw = torch.empty(P, device=x.device, dtype=torch.float32)
+            r = nat.fn(nat.hip_lib(), "qd_reduce_slab", [_p, _p, _i, _i, _f, _p])
+            nat.check(r(nat.ptr(G), nat.ptr(dw), B, P, 0.0, nat.stream_ptr(x.device)), "qd_reduce_slab")
+        else:
+            dw = G.sum(0)
+        dw = dw.view(L, n, 2)
+        if w.dim() == 4:
+            dw = _group_grad(dw, w)
+        return dx, dw, None, None, None, None, None, None
+
+
+def _qsim_noisy_adjoint(x, w, be, noise, shots, T, seed, counter) -> torch.Tensor:
+    n, L = x.shape[1], w.shape[-3]
+    if be == "torch":
+        raise ValueError("the torch backend has no noise model; use hip or cpu")
+    if be not in ("hip", "cpu"):
+        raise ValueError(f"unknown backend {be!r}")
+    if x.device.type != ("cuda" if be == "hip" else "cpu"):
+        raise RuntimeError("hip backend needs CUDA/HIP tensors" if be == "hip" else "cpu backend needs CPU tensors")
+    if be == "hip":
+        _hip_shots_limit(n)
+    _check_noise_shape(n, L)
+    return _QSimNoisyAdjoint.apply(x, w, be, noise, shots, T, int(seed), counter)
+
+
 def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots: Optional[int] = None, seed: int = 0,
          counter=0, diff_method: str = "adjoint", shift_mask: Optional[torch.Tensor] = None,
          noise: Optional["NoiseModel"] = None, trajectories: int = 1) -> torch.Tensor:
@@ -896,7 +1070,16 @@ def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots:
     parameter-shift rule with every shifted circuit measured with the same ``shots``, ``noise`` and
     ``trajectories``, its error sites, shots and readout fields drawn under its own counter
     counter + ((1 + 2p + s) << 48) -- csrc/hip/qsim_onchip.hip.  ``shift_mask`` is allowed; with ``noise=None`` it
-    is ``"parameter_shift"`` bit for bit."""
+    is ``"parameter_shift"`` bit for bit.
+
+    ``diff_method="noisy_adjoint"`` (needs ``noise`` and ``shots``; ``hip`` with n <= 12, or ``cpu``): training
+    against the device model on a simulator.  The forward is the noisy shots call unchanged; the backward
+    differentiates through the circuit with the sampled error gates in it -- the adjoint method run through the
+    Pauli frames the forward drew under the same ``seed`` / ``counter`` / ``trajectories``, weighted by the last
+    frame's outcome flips and the readout thresholds (``noisy_adjoint_rows``; csrc/hip/qsim_nadj.hip).  It is the
+    exact gradient of the forward's mean given those frames, at roughly (1 + rebuilding trajectories) adjoint
+    passes per sample.  A device ``counter`` is read again by the backward: advance it after the backward.
+    ``shift_mask`` is not available."""
     _check_shapes(x, w)
     n = x.shape[1]
     be = backend if backend not in (None, "auto") else default_backend(x.device)
@@ -916,8 +1099,13 @@ def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots:
         T = _check_trajectories(shots, trajectories)
         if diff_method == "adjoint":
             return _qsim_noisy(x, w, be, noise, shots, T, seed, counter)
+        if diff_method == "noisy_adjoint":
+            return _qsim_noisy_adjoint(x, w, be, noise, shots, T, seed, counter)
     elif int(trajectories) != 1:
         raise ValueError("trajectories needs noise")
+    if diff_method == "noisy_adjoint":
+        raise ValueError("diff_method='noisy_adjoint' needs noise= and shots=: it differentiates through the error "
+                         "gates the noisy shots forward samples")
     if diff_method in ("parameter_shift", "on_chip"):
         if be == "torch":
             raise ValueError("the torch backend has no parameter-shift rule; use hip or cpu")

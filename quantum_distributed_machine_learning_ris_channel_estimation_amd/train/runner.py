@@ -539,6 +539,9 @@ class Y2HRunner:
             raise ValueError(f"unknown qsc_diff_method {dm!r}: one of {DIFF_METHODS}")
         if dm == "on_chip" and shots <= 0:
             raise ValueError("qsc_diff_method=on_chip needs qsc_shots > 0: a device measures with finite shots")
+        if dm == "noisy_adjoint" and (shots <= 0 or not any(rates)):
+            raise ValueError("qsc_diff_method=noisy_adjoint needs a qsc_noise_* / qsc_readout* rate and qsc_shots > 0: "
+                             "it differentiates through the error gates the noisy forward samples")
         if self._context().world > 1:
             raise ValueError("qsc_diff_method / qsc_shots / qsc_noise_* train at world size 1 only")
         return {"diff_method": dm, "shots": shots if shots > 0 else None,
