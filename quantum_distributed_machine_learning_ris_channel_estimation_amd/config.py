@@ -89,6 +89,14 @@ class RunnerConfig:
     qsc_readout01: float = 0.0
     qsc_readout10: float = 0.0
     qsc_trajectories: int = 1
+    # qsc_step: where those modes train -- "module" (the default: the path above) or "fused": the fused, graph-captured
+    # step (ops/qsc.py QSCStepHIP's measured modes; on a CPU device the module path).  QOC gradient pruning
+    # (ops/qoc.py; needs parameter_shift or on_chip, either path): after every qsc_prune_accum steps that measure all
+    # parameters, qsc_prune_window steps measure only a sampled (1 - qsc_prune_ratio) of them (0: off)
+    qsc_step: str = "module"
+    qsc_prune_ratio: float = 0.0
+    qsc_prune_accum: int = 1
+    qsc_prune_window: int = 2
 
     def update_from_dict(self, d: Dict[str, Any]) -> "RunnerConfig":
         names = {f.name: f for f in dataclasses.fields(self)}

@@ -380,3 +380,57 @@ QD_API int qd_cpu_sample_z_noisy(const float* probs, const int32_t* amask, const
   }
   return 0;
 }
+
+// ------------------------------------------------------------------------------- QOC gradient pruning
+// The host twin of qd_qoc_update (csrc/hip/qoc.hip; the contract is stated at the top of that file), sequentially:
+// bit-identical acc, mask and step.
+QD_API int qd_cpu_qoc_update(float* acc, uint8_t* mask, int64_t* step, const float* grad, int P, int wa, int wp, int K,
+                             uint64_t seed) {
+  if (!acc || !mask || !step || !grad || P < 2 || P > 4096 || wa < 1 || wa > (1 << 20) || wp < 1 || wp > (1 << 20) ||
+      K < 1 || K > P)
+    return 1;
+  const uint64_t s = (uint64_t)*step, period = (uint64_t)(wa + wp), t = s % period, s1 = s + 1, t1 = s1 % period;
+  if (t == 0)
+    for (int p = 0; p < P; ++p) acc[p] = 0.f;
+  if (t < (uint64_t)wa) {
+    for (int p = 0; p < P; ++p) {
+      const float g = std::fabs(grad[p]), a1 = acc[p] + g;
+      if (std::isfinite(g) && std::isfinite(a1)) acc[p] = a1;
+    }
+  }
+  if (t1 < (uint64_t)wa) {
+    for (int p = 0; p < P; ++p) mask[p] = 1;
+  } else {
+    float m = 0.f;
+    for (int p = 0; p < P; ++p) m = std::max(m, acc[p]);
+    std::vector<uint32_t> q(P);
+    uint64_t S = 0;
+    for (int p = 0; p < P; ++p) {
+      q[p] = m > 0.f ? (uint32_t)std::floor((acc[p] / m) * 1048576.f) + 1u : 1u;
+      S += q[p];
+      mask[p] = 0;
+    }
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    uint32_t rnd[4] = {0, 0, 0, 0};
+    for (int k = 0; k < K; ++k) {
+      if ((k & 3) == 0) {
+        const uint32_t c4[4] = {0x20000000u | (uint32_t)(k >> 2), 0u, (uint32_t)s1, (uint32_t)(s1 >> 32)};
+        qd_cpu_philox4x32(c4, key, rnd);
+      }
+      const uint64_t u = rnd[k & 3];
+      const uint64_t r = u * (S >> 32) + ((u * (S & 0xFFFFFFFFull)) >> 32);
+      uint64_t run = 0;
+      for (int p = 0; p < P; ++p) {
+        run += q[p];
+        if (run > r) {   // (a chosen parameter's q is 0: it cannot be the first to exceed r)
+          S -= q[p];
+          q[p] = 0;
+          mask[p] = 1;
+          break;
+        }
+      }
+    }
+  }
+  *step = (int64_t)s1;
+  return 0;
+}

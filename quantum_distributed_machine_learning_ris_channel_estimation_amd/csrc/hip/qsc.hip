@@ -694,3 +694,43 @@ QD_API int qd_outer_partial(const float* D, const float* P, float* slab, int B, 
                      slab, B, n, F, bs);
   return (int)hipGetLastError();
 }
+
+// The measured training step's hand-over (ops/qsc.py, shots / parameter shift / noise-aware adjoint): the per-sample
+// gradient rows G (B, P = 2nL) of qd_qsim_pshift / qd_qsim_noisy_pshift / qd_qsim_noisy_adjoint become what the fused
+// preprocess backward (qd_qsc2_bwd / qd_qsc2_bwd3) reads, in one launch:
+//   dang[b, q]  = G[b, 2q]                                   (the layer-0 RY columns: d loss / d angle)
+//   qslab[c, p] = sum of G[b, p] over the rows b of chunk c = [64 c, min(B, 64 c + 64)), in ascending b with plain
+//                 fp32 adds from +0, one fixed thread per (c, p): deterministic, no float atomics
+//   mask (nullable; P uint8): qslab[c, p] = +0 where mask[p] == 0 (a parameter whose circuits did not run; its
+//                 layer-0 RY column still feeds dang).
+// Grid: ceil(B / 64) workgroups = the slab's rows; P <= 256 (one column per thread, the fused backward's qwidth limit).
+namespace qd {
+namespace qsc {
+__global__ void __launch_bounds__(256) rows_to_step_kernel(const float* __restrict__ G, const uint8_t* __restrict__ mask,
+                                                           float* __restrict__ dang, float* __restrict__ qslab, int B,
+                                                           int n, int P) {
+  const int c = blockIdx.x, b0 = c * 64, b1 = min(B, b0 + 64);
+  const int p = threadIdx.x;
+  if (p < P) {
+    float s = 0.f;
+    if (!mask || mask[p]) {
+      for (int b = b0; b < b1; ++b) s += G[(size_t)b * P + p];
+    }
+    qslab[(size_t)c * P + p] = s;
+  }
+  for (int i = threadIdx.x; i < (b1 - b0) * n; i += 256) {
+    const int b = b0 + i / n, q = i - (i / n) * n;
+    dang[(size_t)b * n + q] = G[(size_t)b * P + 2 * q];
+  }
+}
+}  // namespace qsc
+}  // namespace qd
+
+QD_API int qd_qsc_rows_to_step(const float* G, const uint8_t* mask, float* dang, float* qslab, int B, int n, int L,
+                               void* stream) {
+  if (!G || !dang || !qslab || B < 1 || n < 1 || L < 1 || n > 128 || L > 128 || 2 * n * L > 256)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(qd::qsc::rows_to_step_kernel, dim3((B + 63) / 64), dim3(256), 0, (hipStream_t)stream, G, mask,
+                     dang, qslab, B, n, 2 * n * L);
+  return (int)hipGetLastError();
+}

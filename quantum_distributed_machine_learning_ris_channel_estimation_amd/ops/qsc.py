@@ -41,10 +41,20 @@ def balanced_grid(samples: int, waves: int, cap: int) -> int:
 
 class QSCStepHIP:
     def __init__(self, model, space: FlatParamSpace, batch_total: int, n_groups: int = 1,
-                 grid_fwd: int = 512, grid_bwd: int = 256, impl: str = "mfma", balance_bwd: bool = True):
+                 grid_fwd: int = 512, grid_bwd: int = 256, impl: str = "mfma", balance_bwd: bool = True,
+                 diff_method: str = "adjoint", shots: Optional[int] = None, noise=None, trajectories: int = 1,
+                 shot_seed: int = 0, shift_mask: Optional[torch.Tensor] = None):
         """impl: "mfma" (csrc/hip/qsc_mfma.hip: one wave per sample, fp32 MFMA convs; default) or
         "ref" (csrc/hip/qsc.hip: one workgroup per sample, VALU convs).  balance_bwd (mfma): shrink the
-        backward's grid below ``grid_bwd`` until every wave takes the same number of samples."""
+        backward's grid below ``grid_bwd`` until every wave takes the same number of samples.
+
+        ``diff_method`` / ``shots`` / ``noise`` / ``trajectories`` / ``shot_seed`` / ``shift_mask`` as for
+        ``ops.quantum.qsim`` (seed = shot_seed): with ``shots`` set or a ``diff_method`` other than "adjoint" the
+        step is *measured* -- the forward's <Z_i> come from the finite-shot / noisy kernels, the backward from the
+        method's own kernel, its per-sample rows handed to the fused preprocess backward by qd_qsc_rows_to_step
+        (csrc/hip/qsc.hip).  The shot streams follow ``shot_ctr`` (a device counter the step owns and advances after
+        every backward).  ``shift_mask``: a CUDA uint8 tensor of 2nL entries held by reference (0 = the parameter's
+        shifted circuits do not run and its gradient is exactly 0); a ``QOCPruner``'s ``mask`` fits."""
         self.m = model
         self.space = space
         dev = space.flat.device
@@ -53,6 +63,7 @@ class QSCStepHIP:
         self.n = model.num_qubits
         self.L = model.n_layers
         self.C = model.n_classes
+        self._init_measured(dev, impl, diff_method, shots, noise, trajectories, shot_seed, shift_mask)
         pre = model.preprocess
         names = dict(zip(space.names, space.offsets))
         o = [names["preprocess.0.weight"], names["preprocess.0.bias"], names["preprocess.3.weight"],
@@ -112,7 +123,8 @@ class QSCStepHIP:
         self.big = self.n > HIP_REG_MAX_QUBITS  # workgroup-per-sample simulator (qsim_big.hip)
         # n = 12: every gate layer -- forward and adjoint -- as complex MFMA mode products (csrc/hip/qsim12_mfma.hip,
         # same contract as qsim_big.hip's kernels); knobs.KNOBS.qsim_mfma12 = False: the VALU kernels
-        self.mfma12 = dev.type == "cuda" and self.n == 12 and 1 <= self.L <= 8 and KNOBS.qsim_mfma12
+        self.mfma12 = dev.type == "cuda" and self.n == 12 and 1 <= self.L <= 8 and KNOBS.qsim_mfma12 \
+            and not self.measured
         # n = 13..16 with >= 2 layers: the streamed simulator (csrc/hip/qsim_stream.hip, one workgroup per
         # (sample, 4096-amplitude brick) per pass); else qsim_big.hip's workgroup-per-sample kernels
         self.stream = self.big and stream_sim_ok(self.n, self.L)
@@ -139,6 +151,8 @@ class QSCStepHIP:
         else:
             self.qrows = nat.fn(L, "qd_qsim_bwd_grid", [_i, _i])(self.n, batch_total)
             self.qws = None
+        if self.measured and self.diff_method != "adjoint":
+            self.qrows = -(-batch_total // 64)   # qd_qsc_rows_to_step: one slab row per 64 samples
         self.qslab = torch.empty(self.qrows, 2 * self.n * self.L, **f32)
         self._pre_fwd = nat.fn(L, "qd_qsc_pre_fwd", [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p])
         self._pre_bwd = nat.fn(L, "qd_qsc_pre_bwd", [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p])
@@ -182,7 +196,7 @@ class QSCStepHIP:
         # (qd_qsim_mfma_prep_noise), so the step has no extra launch.  The adjoint backward reads the final
         # state it saves (qsim.hip's layout).  knobs.KNOBS.qsim_mfma = False: the register forward (qsim.hip).
         self.mfma = (dev.type == "cuda" and not self.big and self.n == 8 and 2 <= self.L <= 8
-                     and self.psave is not None and KNOBS.qsim_mfma)
+                     and self.psave is not None and KNOBS.qsim_mfma and not self.measured)
         if self.mfma:
             halves = nat.fn(L, "qd_qsim_mfma_ops_halves", [_i, _i], ctypes.c_longlong)(max(1, n_groups), self.L)
             self.qops = torch.empty(halves, dtype=torch.float16, device=dev)
@@ -194,11 +208,41 @@ class QSCStepHIP:
         # n = 8: the adjoint backward on the matrix cores too (csrc/hip/qsim12_mfma.hip qd_qsim_mfma8_bwd: the same
         # contract as qd_qsim_bwd_saved, plus its own operand images); knobs.KNOBS.qsim_mfma_bwd = False: qsim.hip
         self.mfma_bwd = (dev.type == "cuda" and not self.big and self.n == 8 and 1 <= self.L <= 8
-                         and self.psave is not None and KNOBS.qsim_mfma_bwd)
+                         and self.psave is not None and KNOBS.qsim_mfma_bwd and not self.measured)
         if self.mfma_bwd:
             nb = nat.fn(L, "qd_qsim_mfma8_workspace", [_i, _i], ctypes.c_longlong)(max(1, n_groups), self.L)
             self.qops8 = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
             self._qb = nat.fn(L, "qd_qsim_mfma8_bwd", [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p])
+
+    def _init_measured(self, dev, impl, diff_method, shots, noise, trajectories, shot_seed, shift_mask) -> None:
+        from . import quantum as Q
+        shots, T = Q._check_measure_args(diff_method, shots, noise, trajectories, shift_mask)
+        Q._check_on_chip_shots(diff_method, shots)
+        Q._check_mask_method(diff_method, shift_mask)
+        self.diff_method, self.noise, self.trajectories = diff_method, noise, T
+        self.shots = Q._check_shots(shots) if shots else None
+        self.shot_seed = int(shot_seed)
+        self.shift_mask = shift_mask
+        self.measured = self.shots is not None or diff_method != "adjoint"
+        if not self.measured:
+            return
+        n, L, P = self.n, self.L, 2 * self.n * self.L
+        if impl != "mfma":
+            raise ValueError(f"a measured step (shots / diff_method) needs impl='mfma', got {impl!r}")
+        Q._hip_shots_limit(n)
+        if P > 256:
+            raise ValueError(f"a measured step supports 2 n L <= 256 (the fused backward's slab width), got n={n} L={L}")
+        if diff_method in ("parameter_shift", "on_chip"):
+            Q._check_pshift_shape(n, L)
+        if noise is not None:
+            Q._check_noise_shape(n, L)
+        if shift_mask is not None and (shift_mask.device.type != "cuda" or shift_mask.dtype != torch.uint8
+                                       or shift_mask.numel() != P or not shift_mask.is_contiguous()):
+            raise ValueError(f"shift_mask must be a contiguous CUDA uint8 tensor of {P} entries")
+        self.shot_ctr = torch.zeros((), dtype=torch.int64, device=dev)   # the call counter of qsim(counter=)
+        if diff_method != "adjoint":
+            self.Grows = torch.empty(self.B, P, device=dev, dtype=torch.float32)   # the method's per-sample rows
+            self._rows = nat.fn(nat.hip_lib(), "qd_qsc_rows_to_step", [_p, _p, _p, _p, _i, _i, _i, _p])
 
     def quantum_weights(self) -> torch.Tensor:
         """Master weights, or (training + QuantumNAT) G per-stream noisy copies drawn in-kernel
@@ -269,7 +313,15 @@ class QSCStepHIP:
         extra = (nat.ptr(self.qws) if self.qws is not None else None,
                  nat.ptr(self.psave) if self.psave is not None else None) if self.big else \
             (nat.ptr(self.psave) if self.psave is not None else None,)
-        if self.mfma:
+        if self.measured and self.shots:
+            from . import quantum as Q
+            if self.noise is not None:
+                Q.hip_qsim_noisy_shots_fwd(self.angles, w, self.E, None, self.noise, self.shots, self.trajectories,
+                                           self.shot_seed, 0, nat.ptr(self.shot_ctr), wgroup)
+            else:
+                Q.hip_qsim_shots_fwd(self.angles, w, self.E, None, self.shots, self.shot_seed, 0,
+                                     nat.ptr(self.shot_ctr), wgroup)
+        elif self.mfma:
             nat.check(self._mfwd(nat.ptr(self.angles), nat.ptr(w), nat.ptr(self.qops), nat.ptr(self.E), B, L, wgroup,
                                  nat.ptr(self.psave), st), "qsim_mfma_fwd")
         else:
@@ -336,14 +388,19 @@ class QSCStepHIP:
             (nat.ptr(self.psave) if self.psave is not None else None,)
         if self.mfma_bwd:
             extra = (nat.ptr(self.qops8), nat.ptr(self.psave))
-        nat.check(self._qb(nat.ptr(self.angles), nat.ptr(w), nat.ptr(self.dE), nat.ptr(self.dang),
-                           nat.ptr(self.qslab), B, n, L, wgroup, *extra, st), "qsim_bwd")
+        qslab, qrows = self.qslab, self.qrows
+        if self.measured:
+            qslab = self._measured_backward(w, wgroup, st)
+            qrows = qslab.shape[0]
+        else:
+            nat.check(self._qb(nat.ptr(self.angles), nat.ptr(w), nat.ptr(self.dE), nat.ptr(self.dang),
+                               nat.ptr(self.qslab), B, n, L, wgroup, *extra, st), "qsim_bwd")
         own = SlabBatch()
         if self.impl != "mfma":   # (the MFMA preprocess backward folds this reduction into its own slab)
             (slabs if slabs is not None else own).add(self.qslab, m.qlayer.weights.grad, 1, self.qrows, 2 * n * L)
         if self.impl == "mfma":
             args = (nat.ptr(x), nat.ptr(flat), self.offs, nat.ptr(self.angles), nat.ptr(self.dang), nat.ptr(self.dpre),
-                    nat.ptr(self.preslab), nat.ptr(self.p2), *self._saved(), nat.ptr(self.qslab), self.qrows, 2 * n * L,
+                    nat.ptr(self.preslab), nat.ptr(self.p2), *self._saved(), nat.ptr(qslab), qrows, 2 * n * L,
                     B, n, self.Hh, self.Ww, self.grid_bwd)
             if self.bwd_x3:
                 nat.check(self._bwd3(*args, nat.ptr(self.w2t_img) if self._img_step else None, st), "qsc2_bwd3")
@@ -365,4 +422,28 @@ class QSCStepHIP:
                                   self.wl_bs, st), "qsc_outer_partial")
             nat.check(self._ssum(nat.ptr(self.wlslab), nat.ptr(self.gwl), 1, self.wlslab.shape[0], self.n * F,
                                  int(accumulate), st), "qsc_wl_slab_sum")
+        if self.measured:   # (the backward re-read the counter the forward read: advance it only now)
+            from .quantum import counter_add
+            counter_add(self.shot_ctr, 1)
         return self.loss
+
+    def _measured_backward(self, w, wgroup: int, st) -> torch.Tensor:
+        """The measured modes' quantum backward: writes ``dang`` and returns the weight-gradient slab (rows, 2nL)
+        the fused preprocess backward reduces."""
+        from . import quantum as Q
+        if self.diff_method == "adjoint":   # straight-through: the exact adjoint of the noiseless circuit
+            return Q.hip_qsim_bwd_slab(self.angles, w, self.dE, self.dang)
+        cptr = nat.ptr(self.shot_ctr)
+        if self.diff_method == "noisy_adjoint":
+            Q.hip_qsim_noisy_adjoint(self.angles, w, self.dE, self.Grows, self.noise, self.trajectories,
+                                     self.shot_seed, 0, cptr, wgroup)
+        elif self.noise is not None:
+            Q.hip_qsim_noisy_pshift(self.angles, w, self.dE, self.Grows, None, None, self.shift_mask, True, self.shots,
+                                    self.shot_seed, 0, cptr, wgroup, self.noise, self.trajectories)
+        else:
+            Q.hip_qsim_pshift(self.angles, w, self.dE, self.Grows, None, None, self.shift_mask, True, self.shots or 0,
+                              self.shot_seed, 0, cptr, wgroup)
+        mask = self.shift_mask
+        nat.check(self._rows(nat.ptr(self.Grows), nat.ptr(mask) if mask is not None else None, nat.ptr(self.dang),
+                             nat.ptr(self.qslab), self.B, self.n, self.L, st), "qsc_rows_to_step")
+        return self.qslab

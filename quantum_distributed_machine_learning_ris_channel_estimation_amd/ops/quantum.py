@@ -1036,6 +1036,42 @@ def _qsim_noisy_adjoint(x, w, be, noise, shots, T, seed, counter) -> torch.Tenso
     return _QSimNoisyAdjoint.apply(x, w, be, noise, shots, T, int(seed), counter)
 
 
+def _check_measure_args(diff_method, shots, noise, trajectories, shift_mask):
+    """The combination rules of ``qsim``'s measurement arguments that hold on every backend (``qsim`` and the fused
+    step, ops/qsc.py, share them): (shots, trajectories), both checked when ``noise`` is set."""
+    if diff_method not in DIFF_METHODS:
+        raise ValueError(f"unknown diff_method {diff_method!r}: one of {DIFF_METHODS}")
+    T = 1
+    if noise is not None:
+        if not isinstance(noise, NoiseModel):
+            raise ValueError(f"noise must be a NoiseModel, got {type(noise).__name__}")
+        if not shots:
+            raise ValueError("noise needs shots: the noise model is sampled per measurement shot")
+        if diff_method == "parameter_shift":
+            raise ValueError("noise with diff_method='parameter_shift' is not supported: "
+                             "diff_method='on_chip' measures the shifted circuits under the noise")
+        if shift_mask is not None and diff_method != "on_chip":
+            raise ValueError("shift_mask needs diff_method='parameter_shift' or 'on_chip'")
+        shots = _check_shots(shots)
+        T = _check_trajectories(shots, trajectories)
+    elif int(trajectories) != 1:
+        raise ValueError("trajectories needs noise")
+    if diff_method == "noisy_adjoint" and noise is None:
+        raise ValueError("diff_method='noisy_adjoint' needs noise= and shots=: it differentiates through the error "
+                         "gates the noisy shots forward samples")
+    return shots, T
+
+
+def _check_on_chip_shots(diff_method, shots) -> None:
+    if diff_method == "on_chip" and not shots:
+        raise ValueError("diff_method='on_chip' needs shots: a device measures every circuit with finite shots")
+
+
+def _check_mask_method(diff_method, shift_mask) -> None:
+    if shift_mask is not None and diff_method not in ("parameter_shift", "on_chip"):
+        raise ValueError("shift_mask needs diff_method='parameter_shift' or 'on_chip'")
+
+
 def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots: Optional[int] = None, seed: int = 0,
          counter=0, diff_method: str = "adjoint", shift_mask: Optional[torch.Tensor] = None,
          noise: Optional["NoiseModel"] = None, trajectories: int = 1) -> torch.Tensor:
@@ -1083,36 +1119,17 @@ def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots:
     _check_shapes(x, w)
     n = x.shape[1]
     be = backend if backend not in (None, "auto") else default_backend(x.device)
-    if diff_method not in DIFF_METHODS:
-        raise ValueError(f"unknown diff_method {diff_method!r}: one of {DIFF_METHODS}")
-    if noise is not None:
-        if not isinstance(noise, NoiseModel):
-            raise ValueError(f"noise must be a NoiseModel, got {type(noise).__name__}")
-        if not shots:
-            raise ValueError("noise needs shots: the noise model is sampled per measurement shot")
-        if diff_method == "parameter_shift":
-            raise ValueError("noise with diff_method='parameter_shift' is not supported: "
-                             "diff_method='on_chip' measures the shifted circuits under the noise")
-        if shift_mask is not None and diff_method != "on_chip":
-            raise ValueError("shift_mask needs diff_method='parameter_shift' or 'on_chip'")
-        shots = _check_shots(shots)
-        T = _check_trajectories(shots, trajectories)
-        if diff_method == "adjoint":
-            return _qsim_noisy(x, w, be, noise, shots, T, seed, counter)
-        if diff_method == "noisy_adjoint":
-            return _qsim_noisy_adjoint(x, w, be, noise, shots, T, seed, counter)
-    elif int(trajectories) != 1:
-        raise ValueError("trajectories needs noise")
-    if diff_method == "noisy_adjoint":
-        raise ValueError("diff_method='noisy_adjoint' needs noise= and shots=: it differentiates through the error "
-                         "gates the noisy shots forward samples")
+    shots, T = _check_measure_args(diff_method, shots, noise, trajectories, shift_mask)
+    if noise is not None and diff_method == "adjoint":
+        return _qsim_noisy(x, w, be, noise, shots, T, seed, counter)
+    if noise is not None and diff_method == "noisy_adjoint":
+        return _qsim_noisy_adjoint(x, w, be, noise, shots, T, seed, counter)
     if diff_method in ("parameter_shift", "on_chip"):
         if be == "torch":
             raise ValueError("the torch backend has no parameter-shift rule; use hip or cpu")
         if be not in ("hip", "cpu"):
             raise ValueError(f"unknown backend {be!r}")
-        if diff_method == "on_chip" and not shots:
-            raise ValueError("diff_method='on_chip' needs shots: a device measures every circuit with finite shots")
+        _check_on_chip_shots(diff_method, shots)
         if be == "hip" and x.device.type == "cuda":
             _hip_shots_limit(n)
         _check_pshift_shape(n, w.shape[-3])
@@ -1122,8 +1139,7 @@ def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots:
             return _QSimPShift.apply(x, w, be, shots, int(seed), counter, shift_mask)
         _check_noise_shape(n, w.shape[-3])
         return _QSimPShift.apply(x, w, be, shots, int(seed), counter, shift_mask, noise, T)
-    if shift_mask is not None:
-        raise ValueError("shift_mask needs diff_method='parameter_shift' or 'on_chip'")
+    _check_mask_method(diff_method, shift_mask)
     if shots:
         shots = _check_shots(shots)
         if be == "torch":

@@ -768,7 +768,8 @@ class ClassifierStep:
                  skip: Optional[torch.Tensor] = None, hip_kw: Optional[dict] = None):
         """``skip``: a shared NaN-guard flag another loss already set this step (it is incremented);
         by default the step owns its flag (``self.skip``, overwritten every step).  ``hip_kw``: extra
-        QSCStepHIP arguments (launch grids)."""
+        QSCStepHIP arguments (launch grids; the measured modes' diff_method / shots / noise / trajectories /
+        shot_seed / shift_mask)."""
         self.model = model
         self.S = n_streams
         self.grad_hook = grad_hook
@@ -823,7 +824,13 @@ class ClassifierStep:
             self._xin[:n].copy_(x[lo:lo + n])
             if n < Bs:
                 self._xin[n:].copy_(x[lo + n - 1:lo + n].expand(Bs - n, *x.shape[1:]))
-            h.infer(self._xin, None, self._logp)
+            if getattr(h, "measured", False) and h.shots:
+                # the step's device model, under host counters from 2^40 up: validation draws never meet training's
+                self._val_calls = getattr(self, "_val_calls", 0) + 1
+                h.infer(self._xin, None, self._logp, shots=h.shots, seed=h.shot_seed,
+                        counter=(1 << 40) + self._val_calls - 1, noise=h.noise, trajectories=h.trajectories)
+            else:
+                h.infer(self._xin, None, self._logp)
             out[lo:lo + n].copy_(self._logp[:n])
         return out
 

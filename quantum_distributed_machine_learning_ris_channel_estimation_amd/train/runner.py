@@ -547,11 +547,26 @@ class Y2HRunner:
         return {"diff_method": dm, "shots": shots if shots > 0 else None,
                 "noise": NoiseModel(*rates) if any(rates) else None, "trajectories": int(self.qsc_trajectories)}
 
+    def qsc_pruner(self, model):
+        """The ``QOCPruner`` of the qsc_prune_* knobs over the quantum layer's 2nL parameters (ops/qoc.py), or None
+        with qsc_prune_ratio = 0.  Pruning skips shifted circuits: it needs a parameter-shift backward."""
+        ratio = float(self.qsc_prune_ratio)
+        if ratio == 0.0:
+            return None
+        if str(self.qsc_diff_method) not in ("parameter_shift", "on_chip"):
+            raise ValueError("qsc_prune_ratio needs qsc_diff_method=parameter_shift or on_chip: the adjoint methods "
+                             "compute every column in one pass")
+        from ..ops.qoc import QOCPruner
+        return QOCPruner(model.qlayer.weights.numel(), ratio, int(self.qsc_prune_accum), int(self.qsc_prune_window),
+                         seed=self.seed, device=self._context().device)
+
     def _train_classifier(self, model, kind: str, opt_name: str, wd: float, prune_thr: float,
                           on_epoch, histories: Tuple[List, List, List], extra: Optional[Dict] = None,
-                          module_path: bool = False):
+                          module_path: bool = False, hip_kw: Optional[Dict] = None, pruner=None):
         """``extra``: small mutable trainer state (e.g. best accuracy) saved in the resume file.  ``module_path``:
-        train through the model's own forward and autograd, ungraphed (the fused step does not cover shots)."""
+        train through the model's own forward and autograd, ungraphed.  ``hip_kw``: the fused step's measured-mode
+        arguments (qsc_step=fused).  ``pruner``: a ``QOCPruner`` updated with the quantum layer's raw gradient after
+        every step, before the optimizer's own threshold pruning; its mask is the step's ``shift_mask``."""
         ctx = self._context()
         tr, va = self.device_stores()
         model = model.to(ctx.device)
@@ -564,7 +579,12 @@ class Y2HRunner:
         S, B = tr.n_streams, self.batch_size_DML
         ref = self._dp_reference()
         Bl = (B + ctx.world - 1) // ctx.world if ref else B
-        cstep = ClassifierStep(model, S) if module_path else ClassifierStep(model, S, space=space, batch_total=S * Bl)
+        if pruner is not None:   # (both paths: the fused step's partial batches run through the module)
+            model.qlayer.shift_mask = pruner.mask.view(model.qlayer.weights.shape)
+            if hip_kw is not None:
+                hip_kw = dict(hip_kw, shift_mask=pruner.mask)
+        cstep = ClassifierStep(model, S) if module_path else ClassifierStep(model, S, space=space, batch_total=S * Bl,
+                                                                            hip_kw=hip_kw)
         skip = cstep.skip if self.nan_guard else None
         buckets = GradBuckets(ctx, {"all": [space.grad] + ([skip] if skip is not None else [])})
         cstep.grad_hook = buckets.launch
@@ -601,6 +621,8 @@ class Y2HRunner:
                 buckets.launch_all()
             loss_acc.add_(loss)
             buckets.wait()
+            if pruner is not None:
+                pruner.update(model.qlayer.weights.grad)
             opt.step(grad_scale=gscale, skip=skip)
 
         graphed = GraphedStep(lambda: run(static_idx), enabled=self._graphs_on() and not module_path)
@@ -613,6 +635,7 @@ class Y2HRunner:
         resume_path = os.path.join(ck.ckpt_dir(self.workspace, self.Pilot_num),
                                    f"{kind.upper()}_{B}_{self.SNRdb}dB_resume.pth")
         start = 0
+        shot_ctr = getattr(cstep.hip, "shot_ctr", None)
         if self.resume:
             st = ck.load_resume(resume_path)
             if st is not None:
@@ -621,6 +644,10 @@ class Y2HRunner:
                 for h, v in zip(histories, st["histories"]):
                     h.extend(v.tolist())
                 extra.update({k: float(v) for k, v in st["extra"].items()})
+                if shot_ctr is not None and "shot_ctr" in st:
+                    shot_ctr.copy_(st["shot_ctr"])
+                if pruner is not None and "pruner" in st:
+                    pruner.load_state_dict(st["pruner"])
                 start = int(st["epoch"]) + 1
                 if ctx.world == 1:
                     ck.set_rng_state(st["rng"])
@@ -638,7 +665,9 @@ class Y2HRunner:
                         _capture_preserving(graphed, [space.flat, opt.step_t, loss_acc, opt.pruned]
                                             + ([opt.m, opt.v] if opt.kind != "sgd" else [opt.buf])
                                             + ([cstep.hip.noise_ctr] if getattr(cstep.hip, "noise_ctr", None)
-                                               is not None else []),
+                                               is not None else [])
+                                            + ([shot_ctr] if shot_ctr is not None else [])
+                                            + (pruner.tensors if pruner is not None else []),
                                             static_idx, idx)
                     static_idx.copy_(idx)
                     graphed()
@@ -665,7 +694,9 @@ class Y2HRunner:
             if ctx.is_main:
                 ck.save_resume(resume_path, epoch=epoch, flat=space.flat.cpu(), optimizer=opt.state_dict(),
                                histories=[torch.tensor(h, dtype=torch.float64) for h in histories],
-                               extra={k: torch.tensor(float(v)) for k, v in extra.items()}, rng=ck.rng_state())
+                               extra={k: torch.tensor(float(v)) for k, v in extra.items()}, rng=ck.rng_state(),
+                               **({"shot_ctr": shot_ctr.cpu()} if shot_ctr is not None else {}),
+                               **({"pruner": pruner.state_dict()} if pruner is not None else {}))
             _maybe_fault(epoch)
         return model
 
@@ -676,10 +707,17 @@ class Y2HRunner:
                          use_gradient_pruning=self.use_gradient_pruning, pilot_num=self.Pilot_num,
                          backend=None if self.backend == "auto" else self.backend, noise_level=self.noise_level,
                          gradient_threshold=self.gradient_threshold, **(self.qsc_device_knobs() or {}))
-        on_chip = self.qsc_device_knobs() is not None
+        knobs = self.qsc_device_knobs()
+        on_chip = knobs is not None
         if on_chip:
             model.qlayer.manual_shot_seed(self.seed)   # the shot streams follow the run's seed
         ctx = self._context()
+        if str(self.qsc_step) not in ("module", "fused"):
+            raise ValueError(f"unknown qsc_step {self.qsc_step!r}: module or fused")
+        # qsc_step=fused: the measured modes run in the fused, graphed step (ops/qsc.py); a CPU device has no fused
+        # step and keeps the module path, as the exact step does
+        fused = on_chip and str(self.qsc_step) == "fused" and ctx.device.type == "cuda"
+        pruner = self.qsc_pruner(model)
         d = ck.ckpt_dir(self.workspace, self.Pilot_num) if ctx.is_main else None
         state = {"best": 0.0}
         self._print("Data Loaded for QSC with QuantumNAT + On-chip QNN optimization!")
@@ -697,7 +735,9 @@ class Y2HRunner:
         prune = self.gradient_threshold if self.use_gradient_pruning else 0.0
         self.qsc_model = self._train_classifier(model, "qsc", "adamw", self.qsc_weight_decay, prune, on_epoch,
                                                 (self.train_QSC_losses, self.val_QSC_losses, self.val_QSC_accuracies),
-                                                extra=state, module_path=on_chip)
+                                                extra=state, module_path=on_chip and not fused,
+                                                hip_kw=dict(knobs, shot_seed=self.seed) if fused else None,
+                                                pruner=pruner)
         return self.qsc_model
 
     def train_SC_P128(self):
