@@ -97,6 +97,14 @@ class RunnerConfig:
     qsc_prune_ratio: float = 0.0
     qsc_prune_accum: int = 1
     qsc_prune_window: int = 2
+    # QuantumNAT post-measurement processing of the QSC's measured <Z_j> (models/estimators.py PostMeasurement, off by
+    # default; qsc_step=module and fused alike, world size 1 only): per-wire normalization over the step's batch, and
+    # with qsc_post_quant_levels >= 2 (needs qsc_post_norm) quantization to that many levels on +-qsc_post_quant_range
+    # with the quadratic penalty qsc_post_quant_weight * mean (z - Q)^2 in the loss
+    qsc_post_norm: bool = False
+    qsc_post_quant_levels: int = 0
+    qsc_post_quant_range: float = 2.0
+    qsc_post_quant_weight: float = 0.0
 
     def update_from_dict(self, d: Dict[str, Any]) -> "RunnerConfig":
         names = {f.name: f for f in dataclasses.fields(self)}
@@ -145,6 +153,10 @@ class EvalConfig:
     qsc_readout01: float = 0.0
     qsc_readout10: float = 0.0
     qsc_trajectories: int = 1
+    # a quantum SC trained with post-measurement normalization (its checkpoint says so): normalize with the statistics
+    # of the evaluated chunk itself ("batch": removes a noisy device's per-wire affine distortion, but a prediction
+    # then depends on the chunk it is in) or with the running statistics of training ("running")
+    qsc_post_stats: str = "batch"
 
     def update_from_dict(self, d: Dict[str, Any]) -> "EvalConfig":
         names = {f.name for f in dataclasses.fields(self)}

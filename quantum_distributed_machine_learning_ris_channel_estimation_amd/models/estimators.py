@@ -131,6 +131,45 @@ class QuantumLayer(nn.Module):
                 f"shot_seed={self.shot_seed}, diff_method={self.diff_method}")
 
 
+class PostMeasurement(nn.Module):
+    """QuantumNAT post-measurement normalization and (``levels`` >= 2) quantization of the measured <Z_j> (B, n):
+    ``ops.postmeas.post_measurement`` with ``BatchNorm1d(n, affine=False)``'s running statistics as buffers.
+
+    Training normalizes with the batch's statistics and updates the running ones; evaluation uses the batch's own
+    statistics (``stats="batch"``, the default: a noisy device's affine distortion of <Z_j> is removed without
+    knowing it, but a prediction depends on the batch it is in) or the running ones (``stats="running"``).
+    ``forward(E, valid=None)`` returns the head's input and leaves the normalized values (detached) in ``self.z`` and
+    ``weight * sum (z - Q)^2 / (valid * n)`` in ``self.penalty`` (a 0-d tensor the loss adds)."""
+
+    def __init__(self, n: int, levels: int = 0, qrange: float = 2.0, weight: float = 0.0, momentum: float = 0.1,
+                 eps: float = 1e-5, stats: str = "batch"):
+        super().__init__()
+        from ..ops.postmeas import STATS, check_quantizer
+        check_quantizer(int(levels), float(qrange), float(weight))
+        if stats not in STATS:
+            raise ValueError(f"unknown post-measurement stats {stats!r}: one of {STATS}")
+        self.n, self.levels, self.qrange, self.weight = int(n), int(levels), float(qrange), float(weight)
+        self.momentum, self.eps, self.stats = float(momentum), float(eps), stats
+        self.register_buffer("running_mean", torch.zeros(n))
+        self.register_buffer("running_var", torch.ones(n))
+        self.penalty = None   # set by every forward, on the input's device
+        self.z = None
+
+    def forward(self, E: torch.Tensor, valid: Optional[int] = None) -> torch.Tensor:
+        from ..ops.postmeas import post_measurement
+        y, z, pen = post_measurement(E, self.running_mean, self.running_var, training=self.training,
+                                     stats=self.stats, momentum=self.momentum, eps=self.eps, levels=self.levels,
+                                     qrange=self.qrange, valid=valid)
+        rows = E.shape[0] if valid is None else int(valid)
+        self.z = z.detach()
+        self.penalty = pen * (self.weight / (rows * self.n))
+        return y
+
+    def extra_repr(self) -> str:
+        return (f"n={self.n}, levels={self.levels}, qrange={self.qrange}, weight={self.weight}, "
+                f"momentum={self.momentum}, eps={self.eps}, stats={self.stats}")
+
+
 class QSC_P128(nn.Module):
     """Quantum scenario classifier (E:107-228).
 
@@ -150,13 +189,23 @@ class QSC_P128(nn.Module):
     ("adjoint", "parameter_shift": the gradient an on-chip QNN measures, "on_chip": that gradient measured
     under ``noise`` too, or "noisy_adjoint": the exact gradient through the sampled error gates), ``noise`` and ``trajectories`` (the device's gate and readout errors under which the
     shots are measured).
+    ``post_norm`` adds QuantumNAT's post-measurement normalization between the measurement and the head
+    (``self.postmeas``, a ``PostMeasurement``; registered last, so the default model's state_dict is untouched), and
+    ``post_quant_levels`` >= 2 its post-measurement quantization to that many levels on +-``post_quant_range`` with
+    the quadratic penalty weighted by ``post_quant_weight``.  Both are off by default.
     """
 
     def __init__(self, n_qubits: int = 6, n_layers: int = 3, n_classes: int = 3, use_quantumnat: bool = True,
                  use_gradient_pruning: bool = True, pilot_num: int = 128, backend: Optional[str] = None,
                  noise_level: float = 0.01, gradient_threshold: float = 0.1, use_quantum: bool = True,
-                 shots: Optional[int] = None, diff_method: str = "adjoint", noise=None, trajectories: int = 1):
+                 shots: Optional[int] = None, diff_method: str = "adjoint", noise=None, trajectories: int = 1,
+                 post_norm: bool = False, post_quant_levels: int = 0, post_quant_range: float = 2.0,
+                 post_quant_weight: float = 0.0):
         super().__init__()
+        from ..ops.postmeas import check_quantizer
+        check_quantizer(int(post_quant_levels), float(post_quant_range), float(post_quant_weight))
+        if post_quant_levels and not post_norm:
+            raise ValueError("post_quant_levels needs post_norm: the quantizer's levels sit on the normalized scale")
         self.use_quantum = use_quantum
         self.num_qubits = n_qubits
         self.n_layers = n_layers
@@ -184,6 +233,17 @@ class QSC_P128(nn.Module):
         self.classifier = nn.Linear(n_qubits, n_classes)
         if not use_quantum:
             self.classical_fallback = nn.Sequential(nn.Linear(n_qubits, n_qubits), nn.Tanh())
+        if post_norm:   # (last: the keys before it are those of the default model, in its order)
+            self.postmeas = PostMeasurement(n_qubits, int(post_quant_levels), float(post_quant_range),
+                                            float(post_quant_weight))
+
+    def post_config(self) -> dict:
+        """The post-measurement arguments this model was built with (checkpoint meta)."""
+        pm = getattr(self, "postmeas", None)
+        if pm is None:
+            return {}
+        return {"post_norm": True, "post_quant_levels": pm.levels, "post_quant_range": pm.qrange,
+                "post_quant_weight": pm.weight}
 
     def quantum_weights(self, generator: Optional[torch.Generator] = None) -> torch.Tensor:
         w = self.qlayer.weights
@@ -198,6 +258,8 @@ class QSC_P128(nn.Module):
             xq = self.qlayer(angles, self.quantum_weights())
         else:
             xq = self.classical_fallback(angles)
+        if getattr(self, "postmeas", None) is not None:
+            xq = self.postmeas(xq)
         return F.log_softmax(self.classifier(xq), dim=1)
 
     @torch.no_grad()

@@ -172,6 +172,16 @@ class QSCStepHIP:
             if (self.bwd_x3 and impl == "mfma") else None
         self._img_step = False   # the image holds this step's weights (the last forward was fwd3)
         self._head = nat.fn(L, "qd_qsc_head", [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p])
+        # the model's PostMeasurement module (QuantumNAT post-measurement normalization / quantization), or None: with
+        # it the heads are csrc/hip/qsc_postmeas.hip's, on the same E and dE -- whatever measured E, whatever reads dE
+        self.pm = getattr(model, "postmeas", None)
+        if self.pm is not None:
+            pm = self.pm
+            if pm.running_mean.device != dev or pm.running_mean.dtype != torch.float32 or pm.n != self.n:
+                raise ValueError("the model's postmeas buffers must be fp32 tensors of n_qubits entries on the step's "
+                                 "device")
+            self._head_pm = nat.fn(L, "qd_qsc_head_pm", [_p] * 10 + [_i] * 5 + [_p, _p, _f, _f, _i, _f, _f, _p, _p])
+            self._infer_pm = nat.fn(L, "qd_qsc_infer_head_pm", [_p] * 5 + [_i] * 5 + [_p, _p, _f, _i, _f, _p])
         if self.big:
             pre = "qd_qsim_stream" if self.stream else ("qd_qsim_mfma12" if self.mfma12 else "qd_qsim_big")
             self._qf = nat.fn(L, pre + "_fwd", [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p])
@@ -328,23 +338,30 @@ class QSCStepHIP:
             nat.check(self._qf(nat.ptr(self.angles), nat.ptr(w), nat.ptr(self.E), B, n, L, wgroup, *extra, st),
                       "qsim_fwd")
         cls = m.classifier
-        nat.check(self._head(nat.ptr(self.E), nat.ptr(cls.weight), nat.ptr(cls.bias), nat.ptr(labels),
-                             nat.ptr(self.dE), nat.ptr(cls.weight.grad), nat.ptr(cls.bias.grad), nat.ptr(self.loss),
-                             nat.ptr(loss_acc) if loss_acc is not None else None,
-                             nat.ptr(skip) if skip is not None else None, int(skip_add), int(accumulate), B, n, self.C,
-                             st), "qsc_head")
+        head = (nat.ptr(self.E), nat.ptr(cls.weight), nat.ptr(cls.bias), nat.ptr(labels),
+                nat.ptr(self.dE), nat.ptr(cls.weight.grad), nat.ptr(cls.bias.grad), nat.ptr(self.loss),
+                nat.ptr(loss_acc) if loss_acc is not None else None,
+                nat.ptr(skip) if skip is not None else None, int(skip_add), int(accumulate), B, n, self.C)
+        if self.pm is not None:   # normalize / quantize E, the head, and dE back through the batch statistics
+            pm = self.pm
+            nat.check(self._head_pm(*head, nat.ptr(pm.running_mean), nat.ptr(pm.running_var), pm.momentum, pm.eps,
+                                    pm.levels, pm.qrange, pm.weight, None, st), "qsc_head_pm")
+        else:
+            nat.check(self._head(*head, st), "qsc_head")
         self._w_cur = w
 
     @torch.no_grad()
     def infer(self, x: torch.Tensor, pred: Optional[torch.Tensor] = None,
               logp: Optional[torch.Tensor] = None, shots: int = 0, seed: int = 0, counter=0, noise=None,
-              trajectories: int = 1) -> None:
+              trajectories: int = 1, valid: Optional[int] = None) -> None:
         """Inference on the HIP kernels (x.shape[0] == B): preprocess CNN, the circuit with the clean
         master weights (no QuantumNAT noise), then a thread-per-sample head -> log-probabilities (B, C)
         and / or the argmax (B,) int64.  ``shots`` > 0: the circuit's <Z_i> are finite-shot estimates
         (csrc/hip/qsim_shots.hip's fused kernel on the angles, n <= 12; ``seed`` / ``counter`` as in
         ops.quantum.qsim).  ``noise`` / ``trajectories`` (with ``shots``): the shots are measured under that
-        ``NoiseModel`` (csrc/hip/qsim_noise.hip)."""
+        ``NoiseModel`` (csrc/hip/qsim_noise.hip).  ``valid`` (a model with ``postmeas``; default B): the real rows
+        of a padded batch -- the batch statistics of the post-measurement normalization go over those only
+        (csrc/hip/qsc_postmeas.hip qd_qsc_infer_head_pm, with the module's ``stats``)."""
         m = self.m
         B, n, L = self.B, self.n, self.L
         assert x.shape[0] == B and x.is_contiguous() and self.impl == "mfma"
@@ -370,9 +387,18 @@ class QSCStepHIP:
                 (nat.ptr(self.psave) if self.psave is not None else None,)
             nat.check(self._qf(nat.ptr(self.angles), nat.ptr(w), nat.ptr(self.E), B, n, L, 0, *extra, st), "qsim_fwd")
         cls = m.classifier
+        head = (nat.ptr(self.E), nat.ptr(cls.weight), nat.ptr(cls.bias), nat.ptr(logp) if logp is not None else None,
+                nat.ptr(pred) if pred is not None else None, B, n, self.C)
+        if self.pm is not None:
+            pm = self.pm
+            valid = B if valid is None else int(valid)
+            if not 1 <= valid <= B:
+                raise ValueError(f"valid must be in [1, {B}], got {valid}")
+            nat.check(self._infer_pm(*head, valid, int(pm.stats == "running"), nat.ptr(pm.running_mean),
+                                     nat.ptr(pm.running_var), pm.eps, pm.levels, pm.qrange, st), "qsc_infer_head_pm")
+            return
         f = nat.fn(nat.hip_lib(), "qd_qsc_infer_head", [_p, _p, _p, _p, _p, _i, _i, _i, _p])
-        nat.check(f(nat.ptr(self.E), nat.ptr(cls.weight), nat.ptr(cls.bias), nat.ptr(logp) if logp is not None else None,
-                    nat.ptr(pred) if pred is not None else None, B, n, self.C, st), "qsc_infer_head")
+        nat.check(f(*head, st), "qsc_infer_head")
 
     def backward_part(self, x: torch.Tensor, accumulate: bool = True, slabs: Optional[SlabBatch] = None) -> torch.Tensor:
         m, sp = self.m, self.space

@@ -68,6 +68,7 @@ def save_qsc(d: str, model: nn.Module, bs: int, snr: int, tag: str, alias: bool 
     atomic_save(sd, os.path.join(d, qsc_names(bs, snr, tag)))
     if alias:
         meta = {"n_qubits": model.num_qubits, "n_layers": model.n_layers, "n_classes": model.n_classes}
+        meta.update(model.post_config() if hasattr(model, "post_config") else {})   # (none with the defaults)
         atomic_save({"model_state_dict": sd, "qsc_config": meta}, os.path.join(d, "QSC_optimized_best.pth"))
 
 

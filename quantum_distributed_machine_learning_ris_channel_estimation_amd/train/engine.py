@@ -804,6 +804,8 @@ class ClassifierStep:
                 noise = torch.randn((self.S,) + tuple(w.shape), device=w.device, dtype=w.dtype)
                 w = w.unsqueeze(0) + m.noise_level * noise
             xq = m.qlayer(angles, w)
+            if getattr(m, "postmeas", None) is not None:   # (over the whole batch, all streams together)
+                xq = m.postmeas(xq)
             return F.log_softmax(m.classifier(xq), dim=1)
         return m(x)
 
@@ -828,9 +830,9 @@ class ClassifierStep:
                 # the step's device model, under host counters from 2^40 up: validation draws never meet training's
                 self._val_calls = getattr(self, "_val_calls", 0) + 1
                 h.infer(self._xin, None, self._logp, shots=h.shots, seed=h.shot_seed,
-                        counter=(1 << 40) + self._val_calls - 1, noise=h.noise, trajectories=h.trajectories)
+                        counter=(1 << 40) + self._val_calls - 1, noise=h.noise, trajectories=h.trajectories, valid=n)
             else:
-                h.infer(self._xin, None, self._logp)
+                h.infer(self._xin, None, self._logp, valid=n)
             out[lo:lo + n].copy_(self._logp[:n])
         return out
 
@@ -857,6 +859,9 @@ class ClassifierStep:
             return loss
         out = self.forward(x)
         loss = F.nll_loss(out, labels)
+        pm = getattr(self.model, "postmeas", None)
+        if pm is not None and pm.levels and pm.weight:   # (the quantization penalty the forward just left there)
+            loss = loss + pm.penalty
         loss.backward()
         bad = (~torch.isfinite(loss.detach())).float().reshape(1)
         if self.skip_add:

@@ -94,6 +94,7 @@ class model_val:
         self.hip_engine = True   # (GPU) the HIP inference engine; False: the models' torch forward
         self._qsc_noise = None
         self.qsc_noise_model()   # (refuses noise rates without qsc_shots)
+        self._post_stats()
         self.results: Dict[str, List[float]] = {}
 
     def load_model_state_dict(self, model, filepath, fallback_key=None):
@@ -112,9 +113,31 @@ class model_val:
             self._qsc_noise = (rates, NoiseModel(*rates))
         return self._qsc_noise[1]
 
+    def _post_stats(self) -> str:
+        from ..ops.postmeas import STATS
+        if str(self.qsc_post_stats) not in STATS:
+            raise ValueError(f"unknown qsc_post_stats {self.qsc_post_stats!r}: one of {STATS}")
+        return str(self.qsc_post_stats)
+
     # ------------------------------------------------------------------ loading
     def _dir(self) -> str:
         return ck.ckpt_dir(self.workspace, self.Pilot_num, make=False)
+
+    def load_qsc(self, fq: str) -> QSC_P128:
+        """The quantum SC of checkpoint ``fq``, built from its own ``qsc_config`` meta (a checkpoint without the
+        post-measurement keys loads as a plain QSC); a PostMeasurement module evaluates with ``qsc_post_stats``."""
+        dev = self.device
+        meta = torch.load(fq, map_location="cpu", weights_only=True).get("qsc_config", {})
+        post = {k: meta[k] for k in ("post_norm", "post_quant_levels", "post_quant_range", "post_quant_weight")
+                if k in meta}
+        qsc = QSC_P128(meta.get("n_qubits", self.n_qubits), meta.get("n_layers", self.n_layers),
+                       meta.get("n_classes", 3), use_quantumnat=False, use_gradient_pruning=False,
+                       pilot_num=self.Pilot_num, backend=None if self.backend == "auto" else self.backend,
+                       **post).to(dev)
+        if getattr(qsc, "postmeas", None) is not None:
+            qsc.postmeas.stats = self._post_stats()
+        self.load_model_state_dict(qsc, fq, fallback_key="model_state_dict")
+        return qsc
 
     def load_models(self):
         d, bs, snr = self._dir(), self.batch_size_DML, self.training_SNRdb
@@ -127,11 +150,7 @@ class model_val:
         qsc = None
         fq = os.path.join(d, "QSC_optimized_best.pth")
         try:
-            meta = torch.load(fq, map_location="cpu", weights_only=True).get("qsc_config", {})
-            qsc = QSC_P128(meta.get("n_qubits", self.n_qubits), meta.get("n_layers", self.n_layers),
-                           meta.get("n_classes", 3), use_quantumnat=False, use_gradient_pruning=False,
-                           pilot_num=self.Pilot_num, backend=None if self.backend == "auto" else self.backend).to(dev)
-            self.load_model_state_dict(qsc, fq, fallback_key="model_state_dict")
+            qsc = self.load_qsc(fq)
         except Exception as e:  # reference: bare except -> classical only (T:81-86)
             print(f"Quantum SC model not found, using classical only ({type(e).__name__})")
             qsc = None

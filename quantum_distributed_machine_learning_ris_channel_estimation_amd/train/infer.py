@@ -180,7 +180,7 @@ class HIPInference:
                 self.sc.forward(self.xq, self.pred)
             else:
                 self.qsc.infer(self.xq, self.pred, shots=shots, seed=seed, counter=lo // self.chunk, noise=noise,
-                               trajectories=trajectories)
+                               trajectories=trajectories, valid=n)
             out[lo:lo + n].copy_(self.pred[:n])
         return out
 

@@ -547,6 +547,18 @@ class Y2HRunner:
         return {"diff_method": dm, "shots": shots if shots > 0 else None,
                 "noise": NoiseModel(*rates) if any(rates) else None, "trajectories": int(self.qsc_trajectories)}
 
+    def qsc_post_knobs(self) -> Dict:
+        """The QSC_P128 arguments of the qsc_post_* knobs ({} with the defaults).  The normalization's statistics go
+        over the step's whole batch: more than one rank would need a collective, so world size 1 only."""
+        if not self.qsc_post_norm and int(self.qsc_post_quant_levels) == 0:
+            return {}
+        if self._context().world > 1:
+            raise ValueError("qsc_post_norm / qsc_post_quant_* train at world size 1 only: the batch statistics would "
+                             "need a collective")
+        return {"post_norm": bool(self.qsc_post_norm), "post_quant_levels": int(self.qsc_post_quant_levels),
+                "post_quant_range": float(self.qsc_post_quant_range),
+                "post_quant_weight": float(self.qsc_post_quant_weight)}
+
     def qsc_pruner(self, model):
         """The ``QOCPruner`` of the qsc_prune_* knobs over the quantum layer's 2nL parameters (ops/qoc.py), or None
         with qsc_prune_ratio = 0.  Pruning skips shifted circuits: it needs a parameter-shift backward."""
@@ -636,6 +648,9 @@ class Y2HRunner:
                                    f"{kind.upper()}_{B}_{self.SNRdb}dB_resume.pth")
         start = 0
         shot_ctr = getattr(cstep.hip, "shot_ctr", None)
+        # the post-measurement running statistics: buffers, not parameters -- they are not in the flat space
+        post = getattr(model, "postmeas", None)
+        post_bufs = [post.running_mean, post.running_var] if post is not None else []
         if self.resume:
             st = ck.load_resume(resume_path)
             if st is not None:
@@ -648,6 +663,9 @@ class Y2HRunner:
                     shot_ctr.copy_(st["shot_ctr"])
                 if pruner is not None and "pruner" in st:
                     pruner.load_state_dict(st["pruner"])
+                if post_bufs and "postmeas" in st:
+                    for t, v in zip(post_bufs, st["postmeas"]):
+                        t.copy_(v)
                 start = int(st["epoch"]) + 1
                 if ctx.world == 1:
                     ck.set_rng_state(st["rng"])
@@ -667,7 +685,7 @@ class Y2HRunner:
                                             + ([cstep.hip.noise_ctr] if getattr(cstep.hip, "noise_ctr", None)
                                                is not None else [])
                                             + ([shot_ctr] if shot_ctr is not None else [])
-                                            + (pruner.tensors if pruner is not None else []),
+                                            + (pruner.tensors if pruner is not None else []) + post_bufs,
                                             static_idx, idx)
                     static_idx.copy_(idx)
                     graphed()
@@ -696,7 +714,8 @@ class Y2HRunner:
                                histories=[torch.tensor(h, dtype=torch.float64) for h in histories],
                                extra={k: torch.tensor(float(v)) for k, v in extra.items()}, rng=ck.rng_state(),
                                **({"shot_ctr": shot_ctr.cpu()} if shot_ctr is not None else {}),
-                               **({"pruner": pruner.state_dict()} if pruner is not None else {}))
+                               **({"pruner": pruner.state_dict()} if pruner is not None else {}),
+                               **({"postmeas": [t.cpu() for t in post_bufs]} if post_bufs else {}))
             _maybe_fault(epoch)
         return model
 
@@ -706,7 +725,8 @@ class Y2HRunner:
         model = QSC_P128(self.n_qubits, self.n_layers, self.n_classes, use_quantumnat=self.use_quantumnat,
                          use_gradient_pruning=self.use_gradient_pruning, pilot_num=self.Pilot_num,
                          backend=None if self.backend == "auto" else self.backend, noise_level=self.noise_level,
-                         gradient_threshold=self.gradient_threshold, **(self.qsc_device_knobs() or {}))
+                         gradient_threshold=self.gradient_threshold, **(self.qsc_device_knobs() or {}),
+                         **self.qsc_post_knobs())
         knobs = self.qsc_device_knobs()
         on_chip = knobs is not None
         if on_chip:
