@@ -428,23 +428,9 @@ QD_API int qd_qsim_noisy_adjoint(const float* x, const float* w, const float* gE
   if (thr1 == nullptr || thr2 == nullptr || thr_ro == nullptr) return (int)hipErrorInvalidValue;
   const int nsplit = qd::qnadj::choose_split(T, n);
   if (nsplit > 1 && work == nullptr) return (int)hipErrorInvalidValue;
-#define CALL_NA(NN)                                                                                          \
-  qd::qnadj::launch<NN>(x, w, gE, G, Ebar, frames_out, work, (const uint32_t*)thr1, (const uint32_t*)thr2,   \
-                        (const uint32_t*)thr_ro, B, L, wgroup, T, nsplit, seed, ctr0,                        \
-                        (const unsigned long long*)counter, (hipStream_t)stream)
-  switch (n) {
-    case 2: return CALL_NA(2);
-    case 3: return CALL_NA(3);
-    case 4: return CALL_NA(4);
-    case 5: return CALL_NA(5);
-    case 6: return CALL_NA(6);
-    case 7: return CALL_NA(7);
-    case 8: return CALL_NA(8);
-    case 9: return CALL_NA(9);
-    case 10: return CALL_NA(10);
-    case 11: return CALL_NA(11);
-    case 12: return CALL_NA(12);
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef CALL_NA
+  return dispatch_qubits(n, [&](auto N) {
+    return qd::qnadj::launch<N>(x, w, gE, G, Ebar, frames_out, work, (const uint32_t*)thr1, (const uint32_t*)thr2,
+                                (const uint32_t*)thr_ro, B, L, wgroup, T, nsplit, seed, ctr0,
+                                (const unsigned long long*)counter, (hipStream_t)stream);
+  });
 }

@@ -270,25 +270,11 @@ QD_API int qd_qsim_noisy_shots_fwd(const float* x, const float* w, float* E, int
   if (thr1 == nullptr || thr2 == nullptr || thr_ro == nullptr) return (int)hipErrorInvalidValue;
   const int nsplit = g_force_split > 0 ? g_force_split : choose_split(T, n);
   if (T % nsplit != 0) return (int)hipErrorInvalidValue;
-#define CALL_N(NN)                                                                                             \
-  launch_noisy<NN>(x, w, E, counts, probs_out, frames_out, (const uint32_t*)thr1, (const uint32_t*)thr2,       \
-                   (const uint32_t*)thr_ro, B, L, wgroup, shots, T, nsplit, seed, ctr0, (const unsigned long long*)counter, \
-                   (hipStream_t)stream)
-  switch (n) {
-    case 2: return CALL_N(2);
-    case 3: return CALL_N(3);
-    case 4: return CALL_N(4);
-    case 5: return CALL_N(5);
-    case 6: return CALL_N(6);
-    case 7: return CALL_N(7);
-    case 8: return CALL_N(8);
-    case 9: return CALL_N(9);
-    case 10: return CALL_N(10);
-    case 11: return CALL_N(11);
-    case 12: return CALL_N(12);
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef CALL_N
+  return dispatch_qubits(n, [&](auto N) {
+    return launch_noisy<N>(x, w, E, counts, probs_out, frames_out, (const uint32_t*)thr1, (const uint32_t*)thr2,
+                           (const uint32_t*)thr_ro, B, L, wgroup, shots, T, nsplit, seed, ctr0,
+                           (const unsigned long long*)counter, (hipStream_t)stream);
+  });
 }
 
 // Tests and timing: launch nsplit (1, 2, 4, 8) chunks per sample from now on; 0 = choose again.  A forced split that

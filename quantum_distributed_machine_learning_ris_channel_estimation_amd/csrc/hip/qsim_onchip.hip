@@ -424,23 +424,9 @@ QD_API int qd_qsim_noisy_pshift(const float* x, const float* w, const float* gE,
   if ((long long)B * L * n > 0x7fffffffll) return (int)hipErrorInvalidValue;
   if (wgroup > 0 && B % wgroup != 0) return (int)hipErrorInvalidValue;
   if (thr1 == nullptr || thr2 == nullptr || thr_ro == nullptr) return (int)hipErrorInvalidValue;
-#define CALL_OC(NN)                                                                                              \
-  qd::qonchip::launch<NN>(x, w, gE, G, Epm, probs, frames_out, mask, (const uint32_t*)thr1, (const uint32_t*)thr2, \
-                          (const uint32_t*)thr_ro, B, L, wgroup, need_dx, shots, T, seed, ctr0,                  \
-                          (const unsigned long long*)counter, (hipStream_t)stream)
-  switch (n) {
-    case 2: return CALL_OC(2);
-    case 3: return CALL_OC(3);
-    case 4: return CALL_OC(4);
-    case 5: return CALL_OC(5);
-    case 6: return CALL_OC(6);
-    case 7: return CALL_OC(7);
-    case 8: return CALL_OC(8);
-    case 9: return CALL_OC(9);
-    case 10: return CALL_OC(10);
-    case 11: return CALL_OC(11);
-    case 12: return CALL_OC(12);
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef CALL_OC
+  return dispatch_qubits(n, [&](auto N) {
+    return qd::qonchip::launch<N>(x, w, gE, G, Epm, probs, frames_out, mask, (const uint32_t*)thr1,
+                                  (const uint32_t*)thr2, (const uint32_t*)thr_ro, B, L, wgroup, need_dx, shots, T, seed,
+                                  ctr0, (const unsigned long long*)counter, (hipStream_t)stream);
+  });
 }

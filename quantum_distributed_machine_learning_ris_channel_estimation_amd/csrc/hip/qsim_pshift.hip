@@ -236,22 +236,8 @@ QD_API int qd_qsim_pshift(const float* x, const float* w, const float* gE, float
   if (4ll * n * L + 1 >= (1ll << 16)) return (int)hipErrorInvalidValue;   // stream ids 0 .. 2 P fit 16 bits
   if ((long long)B * L * n > 0x7fffffffll) return (int)hipErrorInvalidValue;
   if (wgroup > 0 && B % wgroup != 0) return (int)hipErrorInvalidValue;
-#define CALL_PS(NN)                                                                                            \
-  qd::qpshift::launch<NN>(x, w, gE, G, Epm, probs, mask, B, L, wgroup, need_dx, shots, seed, ctr0,             \
-                          (const unsigned long long*)counter, (hipStream_t)stream)
-  switch (n) {
-    case 2: return CALL_PS(2);
-    case 3: return CALL_PS(3);
-    case 4: return CALL_PS(4);
-    case 5: return CALL_PS(5);
-    case 6: return CALL_PS(6);
-    case 7: return CALL_PS(7);
-    case 8: return CALL_PS(8);
-    case 9: return CALL_PS(9);
-    case 10: return CALL_PS(10);
-    case 11: return CALL_PS(11);
-    case 12: return CALL_PS(12);
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef CALL_PS
+  return dispatch_qubits(n, [&](auto N) {
+    return qd::qpshift::launch<N>(x, w, gE, G, Epm, probs, mask, B, L, wgroup, need_dx, shots, seed, ctr0,
+                                  (const unsigned long long*)counter, (hipStream_t)stream);
+  });
 }

@@ -116,31 +116,13 @@ static int launch_shots(const float* x, const float* w, float* E, int* counts, i
 
 using namespace qd::qshots;
 
-#define QD_SHOTS_DISPATCH(n, CALL)             \
-  switch (n) {                                 \
-    case 2: return CALL(2);                    \
-    case 3: return CALL(3);                    \
-    case 4: return CALL(4);                    \
-    case 5: return CALL(5);                    \
-    case 6: return CALL(6);                    \
-    case 7: return CALL(7);                    \
-    case 8: return CALL(8);                    \
-    case 9: return CALL(9);                    \
-    case 10: return CALL(10);                  \
-    case 11: return CALL(11);                  \
-    case 12: return CALL(12);                  \
-    default: return (int)hipErrorInvalidValue; \
-  }
-
 static bool shots_ok(int n, int shots) { return n >= 2 && n <= kMaxQubits && shots >= 1 && shots <= kMaxShots; }
 
 // probs (B, 2^n) fp32 = |amp_k|^2 of the circuit's final state, natural basis order.
 QD_API int qd_qsim_probs(const float* x, const float* w, float* probs, int B, int n, int L, int wgroup, void* stream) {
   if (n < 2 || n > kMaxQubits || B < 1 || L < 1) return (int)hipErrorInvalidValue;
   if (wgroup > 0 && B % wgroup != 0) return (int)hipErrorInvalidValue;
-#define CALL_P(NN) launch_probs<NN>(x, w, probs, B, L, wgroup, (hipStream_t)stream)
-  QD_SHOTS_DISPATCH(n, CALL_P)
-#undef CALL_P
+  return dispatch_qubits(n, [&](auto N) { return launch_probs<N>(x, w, probs, B, L, wgroup, (hipStream_t)stream); });
 }
 
 // E (B, n) fp32 and counts (B, n) int32 (nullable) from `shots` draws of every row of probs (B, 2^n) fp32, a
@@ -148,10 +130,10 @@ QD_API int qd_qsim_probs(const float* x, const float* w, float* probs, int B, in
 QD_API int qd_sample_z(const float* probs, float* E, int* counts, int B, int n, int shots, unsigned long long seed,
                        unsigned long long ctr0, const void* counter, void* stream) {
   if (!shots_ok(n, shots) || B < 1) return (int)hipErrorInvalidValue;
-#define CALL_S(NN) \
-  launch_sample<NN>(probs, E, counts, B, shots, seed, ctr0, (const unsigned long long*)counter, (hipStream_t)stream)
-  QD_SHOTS_DISPATCH(n, CALL_S)
-#undef CALL_S
+  return dispatch_qubits(n, [&](auto N) {
+    return launch_sample<N>(probs, E, counts, B, shots, seed, ctr0, (const unsigned long long*)counter,
+                            (hipStream_t)stream);
+  });
 }
 
 // The fused path: state -> probabilities -> shots in one launch.
@@ -160,11 +142,10 @@ QD_API int qd_qsim_shots_fwd(const float* x, const float* w, float* E, int* coun
                              void* stream) {
   if (!shots_ok(n, shots) || B < 1 || L < 1) return (int)hipErrorInvalidValue;
   if (wgroup > 0 && B % wgroup != 0) return (int)hipErrorInvalidValue;
-#define CALL_F(NN)                                                                                  \
-  launch_shots<NN>(x, w, E, counts, B, L, wgroup, shots, seed, ctr0, (const unsigned long long*)counter, \
-                   (hipStream_t)stream)
-  QD_SHOTS_DISPATCH(n, CALL_F)
-#undef CALL_F
+  return dispatch_qubits(n, [&](auto N) {
+    return launch_shots<N>(x, w, E, counts, B, L, wgroup, shots, seed, ctr0, (const unsigned long long*)counter,
+                           (hipStream_t)stream);
+  });
 }
 
 // *counter += delta (one thread): launched after a sampling launch, so that every replay of a captured graph draws

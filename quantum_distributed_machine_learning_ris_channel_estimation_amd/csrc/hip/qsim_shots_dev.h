@@ -18,6 +18,27 @@ constexpr int NW = NT / 64;
 constexpr int kMaxQubits = 12;
 constexpr int kMaxShots = 1 << 20;
 
+// Host side of every launcher: the kernels are instantiated per qubit count, so a runtime n in 2 .. kMaxQubits becomes
+// f(std::integral_constant<int, n>{}) (f returns the launch's status); hipErrorInvalidValue outside that range.
+template <typename F>
+static inline int dispatch_qubits(int n, F&& f) {
+  switch (n) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 9: return f(std::integral_constant<int, 9>{});
+    case 10: return f(std::integral_constant<int, 10>{});
+    case 11: return f(std::integral_constant<int, 11>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    default: return (int)hipErrorInvalidValue;
+  }
+}
+static_assert(kMaxQubits == 12, "dispatch_qubits covers 2 .. kMaxQubits");
+
 // LDS carve (bytes): trig (<= 12 float4) | wave totals of the scan (NW) | per-wave bit counts (NW x 12) | data: the
 // state (2^n complex), or the CDF (2^n words + pads: never larger) -- in the fused kernel one after the other
 constexpr int O_TRIG = 0, O_WTOT = 256, O_WCNT = 272, O_DATA = 512;

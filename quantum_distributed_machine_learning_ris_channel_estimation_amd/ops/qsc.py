@@ -27,7 +27,8 @@ from .. import _native as nat
 from .slabsum import SlabBatch
 from ..ops.optim import FlatParamSpace
 from ..knobs import KNOBS
-from ..ops.quantum import HIP_REG_MAX_QUBITS, stream_sim_ok
+from ..ops.quantum import (HIP_REG_MAX_QUBITS, HIP_SHOTS_MAX_QUBITS, counter_add, hip_measured_fwd, hip_measured_rows,
+                           hip_qsim_bwd_slab, resolve_measure, split_counter, stream_sim_ok)
 
 _p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 
@@ -192,7 +193,6 @@ class QSCStepHIP:
             self.psave = torch.empty(batch_total * (8 << self.n), dtype=torch.uint8, device=dev)
             self._qf = nat.fn(L, "qd_qsim_fwd_save", [_p, _p, _p, _i, _i, _i, _i, _p, _p])
             self._qb = nat.fn(L, "qd_qsim_bwd_saved", [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p])
-        self._rs = nat.fn(L, "qd_reduce_slab", [_p, _p, _i, _i, _f, _p])
         self._ssum = nat.fn(L, "qd_slab_rows_sum", [_p, _p, _i, _i, _i, _i, _p])
         self._outer = nat.fn(L, "qd_outer_partial", [_p, _p, _p, _i, _i, _i, _i, _p])
         self._qnoise = nat.fn(L, "qd_qnoise", [_p, _p, _i, _i, _f, ctypes.c_ulonglong, _p, _p])
@@ -225,27 +225,19 @@ class QSCStepHIP:
             self._qb = nat.fn(L, "qd_qsim_mfma8_bwd", [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p])
 
     def _init_measured(self, dev, impl, diff_method, shots, noise, trajectories, shot_seed, shift_mask) -> None:
-        from . import quantum as Q
-        shots, T = Q._check_measure_args(diff_method, shots, noise, trajectories, shift_mask)
-        Q._check_on_chip_shots(diff_method, shots)
-        Q._check_mask_method(diff_method, shift_mask)
-        self.diff_method, self.noise, self.trajectories = diff_method, noise, T
-        self.shots = Q._check_shots(shots) if shots else None
+        n, L, P = self.n, self.L, 2 * self.n * self.L
+        self.measured = bool(shots) or diff_method != "adjoint"
+        if self.measured and impl != "mfma":
+            raise ValueError(f"a measured step (shots / diff_method) needs impl='mfma', got {impl!r}")
+        if self.measured and P > 256 and n <= HIP_SHOTS_MAX_QUBITS:   # (above 12 qubits the resolver refuses first)
+            raise ValueError(f"a measured step supports 2 n L <= 256 (the fused backward's slab width), got n={n} L={L}")
+        self.mode = mode = resolve_measure(diff_method, shots, noise, trajectories, shift_mask, n, L, "hip", dev,
+                                           mask_shape=False)
+        self.diff_method, self.noise, self.trajectories, self.shots = diff_method, noise, mode.trajectories, mode.shots
         self.shot_seed = int(shot_seed)
         self.shift_mask = shift_mask
-        self.measured = self.shots is not None or diff_method != "adjoint"
         if not self.measured:
             return
-        n, L, P = self.n, self.L, 2 * self.n * self.L
-        if impl != "mfma":
-            raise ValueError(f"a measured step (shots / diff_method) needs impl='mfma', got {impl!r}")
-        Q._hip_shots_limit(n)
-        if P > 256:
-            raise ValueError(f"a measured step supports 2 n L <= 256 (the fused backward's slab width), got n={n} L={L}")
-        if diff_method in ("parameter_shift", "on_chip"):
-            Q._check_pshift_shape(n, L)
-        if noise is not None:
-            Q._check_noise_shape(n, L)
         if shift_mask is not None and (shift_mask.device.type != "cuda" or shift_mask.dtype != torch.uint8
                                        or shift_mask.numel() != P or not shift_mask.is_contiguous()):
             raise ValueError(f"shift_mask must be a contiguous CUDA uint8 tensor of {P} entries")
@@ -324,13 +316,7 @@ class QSCStepHIP:
                  nat.ptr(self.psave) if self.psave is not None else None) if self.big else \
             (nat.ptr(self.psave) if self.psave is not None else None,)
         if self.measured and self.shots:
-            from . import quantum as Q
-            if self.noise is not None:
-                Q.hip_qsim_noisy_shots_fwd(self.angles, w, self.E, None, self.noise, self.shots, self.trajectories,
-                                           self.shot_seed, 0, nat.ptr(self.shot_ctr), wgroup)
-            else:
-                Q.hip_qsim_shots_fwd(self.angles, w, self.E, None, self.shots, self.shot_seed, 0,
-                                     nat.ptr(self.shot_ctr), wgroup)
+            hip_measured_fwd(self.angles, w, self.E, self.mode, self.shot_seed, 0, nat.ptr(self.shot_ctr), wgroup)
         elif self.mfma:
             nat.check(self._mfwd(nat.ptr(self.angles), nat.ptr(w), nat.ptr(self.qops), nat.ptr(self.E), B, L, wgroup,
                                  nat.ptr(self.psave), st), "qsim_mfma_fwd")
@@ -371,16 +357,9 @@ class QSCStepHIP:
         if noise is not None and not shots:
             raise ValueError("noise needs shots")
         if shots:
-            from . import quantum as Q
-            Q._hip_shots_limit(n)
-            ctr0, cptr = Q._split_counter(counter, x.device)
-            shots = Q._check_shots(shots)
-            if noise is not None:
-                Q._check_noise_shape(n, L)
-                Q.hip_qsim_noisy_shots_fwd(self.angles, w, self.E, None, noise, shots,
-                                           Q._check_trajectories(shots, trajectories), int(seed), ctr0, cptr)
-            else:
-                Q.hip_qsim_shots_fwd(self.angles, w, self.E, None, shots, int(seed), ctr0, cptr)
+            mode = resolve_measure("adjoint", shots, noise, trajectories if noise is not None else 1, None, n, L,
+                                   "hip", x.device)
+            hip_measured_fwd(self.angles, w, self.E, mode, int(seed), *split_counter(counter, x.device))
         else:
             extra = (nat.ptr(self.qws) if self.qws is not None else None,
                      nat.ptr(self.psave) if self.psave is not None else None) if self.big else \
@@ -449,26 +428,16 @@ class QSCStepHIP:
             nat.check(self._ssum(nat.ptr(self.wlslab), nat.ptr(self.gwl), 1, self.wlslab.shape[0], self.n * F,
                                  int(accumulate), st), "qsc_wl_slab_sum")
         if self.measured:   # (the backward re-read the counter the forward read: advance it only now)
-            from .quantum import counter_add
             counter_add(self.shot_ctr, 1)
         return self.loss
 
     def _measured_backward(self, w, wgroup: int, st) -> torch.Tensor:
         """The measured modes' quantum backward: writes ``dang`` and returns the weight-gradient slab (rows, 2nL)
         the fused preprocess backward reduces."""
-        from . import quantum as Q
         if self.diff_method == "adjoint":   # straight-through: the exact adjoint of the noiseless circuit
-            return Q.hip_qsim_bwd_slab(self.angles, w, self.dE, self.dang)
-        cptr = nat.ptr(self.shot_ctr)
-        if self.diff_method == "noisy_adjoint":
-            Q.hip_qsim_noisy_adjoint(self.angles, w, self.dE, self.Grows, self.noise, self.trajectories,
-                                     self.shot_seed, 0, cptr, wgroup)
-        elif self.noise is not None:
-            Q.hip_qsim_noisy_pshift(self.angles, w, self.dE, self.Grows, None, None, self.shift_mask, True, self.shots,
-                                    self.shot_seed, 0, cptr, wgroup, self.noise, self.trajectories)
-        else:
-            Q.hip_qsim_pshift(self.angles, w, self.dE, self.Grows, None, None, self.shift_mask, True, self.shots or 0,
-                              self.shot_seed, 0, cptr, wgroup)
+            return hip_qsim_bwd_slab(self.angles, w, self.dE, self.dang)
+        hip_measured_rows(self.angles, w, self.dE, self.Grows, self.mode, self.shift_mask, self.shot_seed, 0,
+                          nat.ptr(self.shot_ctr), wgroup)
         mask = self.shift_mask
         nat.check(self._rows(nat.ptr(self.Grows), nat.ptr(mask) if mask is not None else None, nat.ptr(self.dang),
                              nat.ptr(self.qslab), self.B, self.n, self.L, st), "qsc_rows_to_step")

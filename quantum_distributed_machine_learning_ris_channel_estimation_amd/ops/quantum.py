@@ -39,10 +39,14 @@ Noise-aware adjoint (``qsim(..., shots=N, noise=, trajectories=T, diff_method="n
 method run through every trajectory's framed circuit, what QuantumNAT's noise injection differentiates on a
 simulator; csrc/hip/qsim_nadj.hip (n <= 12) on ``hip``, the parameter-shift rule over ``qsim_probs(frames=)`` in
 fp64 on ``cpu``.
+
+The measurement arguments of all of these are validated in one place, ``resolve_measure``, into a ``MeasureMode``;
+``qsim`` and the fused step (ops/qsc.py) select their kernels from it through ``hip_measured_fwd`` / ``hip_measured_rows``.
 """
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import math
 from typing import Optional
 
@@ -53,6 +57,29 @@ from .. import _native as nat
 _i = ctypes.c_int
 _f = ctypes.c_float
 _p = ctypes.c_void_p
+
+
+def _opt(t: Optional[torch.Tensor]):
+    return nat.ptr(t) if t is not None else None
+
+
+def _check_backend(be: str, device: Optional[torch.device] = None) -> None:
+    """``be`` names a backend, and (given their device) the tensors live where it computes."""
+    if be not in ("hip", "cpu", "torch"):
+        raise ValueError(f"unknown backend {be!r}")
+    if be == "hip" and device is not None and device.type != "cuda":
+        raise RuntimeError("hip backend needs CUDA/HIP tensors")
+    if be == "cpu" and device is not None and device.type != "cpu":
+        raise RuntimeError("cpu backend needs CPU tensors")
+
+
+def reduce_slab(slab: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out (P) fp32 = the column sums of slab (rows, P) fp32, on the current stream and in a fixed order
+    (deterministic: no float atomics)."""
+    name = "qd_reduce_slab"
+    r = nat.fn(nat.hip_lib(), name, [_p, _p, _i, _i, _f, _p])
+    nat.check(r(nat.ptr(slab), nat.ptr(out), slab.shape[0], slab.shape[1], 0.0, nat.stream_ptr(slab.device)), name)
+    return out
 
 HIP_REG_MAX_QUBITS = 10   # register-resident kernel
 HIP_MAX_QUBITS = 16       # workgroup-per-sample kernel above that
@@ -155,10 +182,7 @@ class _QSimHIP(torch.autograd.Function):
         dx = torch.empty_like(x)
         dw = torch.zeros(P, device=x.device, dtype=torch.float32)
         if B > 0:
-            slab = hip_qsim_bwd_slab(x, w, gE, dx)
-            r = nat.fn(nat.hip_lib(), "qd_reduce_slab", [_p, _p, _i, _i, _f, _p])
-            nat.check(r(nat.ptr(slab), nat.ptr(dw), slab.shape[0], P, 0.0, nat.stream_ptr(x.device)),
-                      "qd_reduce_slab")
+            reduce_slab(hip_qsim_bwd_slab(x, w, gE, dx), dw)
         dw = dw.view(L, n, 2)
         if w.dim() == 4:  # grouped (noisy) weights: every group maps back to the same master weights
             dw = _group_grad(dw, w)
@@ -285,7 +309,7 @@ def _check_shots(shots: int) -> int:
     return shots
 
 
-def _split_counter(counter, device):
+def split_counter(counter, device):
     """(host counter, device counter pointer or None): an int is the host part; a CUDA int64 / uint64 scalar
     tensor is read by the kernel (graph replays see its current value; follow the call with counter_add)."""
     if isinstance(counter, torch.Tensor):
@@ -300,7 +324,7 @@ def _split_counter(counter, device):
 def counter_add(counter: torch.Tensor, delta: int = 1) -> None:
     """``counter += delta`` on the current stream (a one-thread kernel, graph-capturable): launch it after a
     sampling call that reads ``counter``, so that every replay of a captured graph draws fresh shots."""
-    _split_counter(counter, counter.device)
+    split_counter(counter, counter.device)
     f = nat.fn(nat.hip_lib(), "qd_counter_add", [_p, _u64, _p])
     nat.check(f(nat.ptr(counter), int(delta) & _M64, nat.stream_ptr(counter.device)), "qd_counter_add")
 
@@ -317,8 +341,8 @@ def hip_sample_z(probs: torch.Tensor, E: torch.Tensor, counts: Optional[torch.Te
                  seed: int = 0, ctr0: int = 0, counter_ptr=None) -> None:
     """Raw launcher: E (B, n) fp32 / counts (B, n) int32 (nullable) from `shots` draws of every row of probs."""
     f = nat.fn(nat.hip_lib(), "qd_sample_z", [_p, _p, _p, _i, _i, _i, _u64, _u64, _p, _p])
-    nat.check(f(nat.ptr(probs), nat.ptr(E), nat.ptr(counts) if counts is not None else None, probs.shape[0], n, shots,
-                seed & _M64, ctr0 & _M64, counter_ptr, nat.stream_ptr(probs.device)), "qd_sample_z")
+    nat.check(f(nat.ptr(probs), nat.ptr(E), _opt(counts), probs.shape[0], n, shots, seed & _M64, ctr0 & _M64,
+                counter_ptr, nat.stream_ptr(probs.device)), "qd_sample_z")
 
 
 def hip_qsim_shots_fwd(x: torch.Tensor, w: torch.Tensor, E: torch.Tensor, counts: Optional[torch.Tensor], shots: int,
@@ -326,9 +350,8 @@ def hip_qsim_shots_fwd(x: torch.Tensor, w: torch.Tensor, E: torch.Tensor, counts
     """Raw launcher of the fused kernel: state -> probabilities -> shots in one launch; n <= 12."""
     B, n = x.shape
     f = nat.fn(nat.hip_lib(), "qd_qsim_shots_fwd", [_p, _p, _p, _p, _i, _i, _i, _i, _i, _u64, _u64, _p, _p])
-    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(E), nat.ptr(counts) if counts is not None else None, B, n,
-                w.shape[-3], wgroup, shots, seed & _M64, ctr0 & _M64, counter_ptr, nat.stream_ptr(x.device)),
-              "qd_qsim_shots_fwd")
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(E), _opt(counts), B, n, w.shape[-3], wgroup, shots, seed & _M64,
+                ctr0 & _M64, counter_ptr, nat.stream_ptr(x.device)), "qd_qsim_shots_fwd")
 
 
 def _hip_shots_limit(n: int) -> None:
@@ -350,9 +373,8 @@ def qsim_probs(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None,
     be = backend if backend not in (None, "auto") else default_backend(x.device)
     if frames is not None:
         return _qsim_probs_framed(x, w, be, frames)
+    _check_backend(be, x.device)
     if be == "hip":
-        if x.device.type != "cuda":
-            raise RuntimeError("hip backend needs CUDA/HIP tensors")
         _hip_shots_limit(n)
         x = x.detach().float().contiguous()
         w = w.detach().float().contiguous()
@@ -362,18 +384,14 @@ def qsim_probs(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None,
         return probs
     if w.dim() == 4:  # host backends: run per group
         return torch.cat([qsim_probs(xc, w[g], be) for g, xc in enumerate(x.chunk(w.shape[0]))], dim=0)
-    if be == "cpu":
-        if x.device.type != "cpu":
-            raise RuntimeError("cpu backend needs CPU tensors")
-        x = x.detach().float().contiguous()
-        w = w.detach().float().contiguous()
-        probs = torch.empty(B, 1 << n, dtype=torch.float64)
-        f = nat.fn(nat.cpu_lib(), "qd_cpu_qsim_probs", [_p, _p, _p, _i, _i, _i])
-        nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(probs), B, n, w.shape[0]), "qd_cpu_qsim_probs")
-        return probs
     if be == "torch":
         return qsim_torch(x, w, return_probs=True)
-    raise ValueError(f"unknown backend {be!r}")
+    x = x.detach().float().contiguous()
+    w = w.detach().float().contiguous()
+    probs = torch.empty(B, 1 << n, dtype=torch.float64)
+    f = nat.fn(nat.cpu_lib(), "qd_cpu_qsim_probs", [_p, _p, _p, _i, _i, _i])
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(probs), B, n, w.shape[0]), "qd_cpu_qsim_probs")
+    return probs
 
 
 @torch.no_grad()
@@ -391,7 +409,7 @@ def sample_z(probs: torch.Tensor, shots: int, seed: int = 0, counter=0, return_c
     if n > HIP_SHOTS_MAX_QUBITS:   # (the host sampler keeps the kernels' range: one contract)
         raise NotImplementedError(f"the shot samplers support n <= {HIP_SHOTS_MAX_QUBITS} qubits, got {n}")
     probs = probs.detach().float().contiguous()
-    ctr0, cptr = _split_counter(counter, probs.device)
+    ctr0, cptr = split_counter(counter, probs.device)
     E = torch.empty(B, n, device=probs.device, dtype=torch.float32)
     counts = torch.empty(B, n, device=probs.device, dtype=torch.int32)
     if B > 0 and probs.device.type == "cuda":
@@ -401,42 +419,6 @@ def sample_z(probs: torch.Tensor, shots: int, seed: int = 0, counter=0, return_c
         nat.check(f(nat.ptr(probs), nat.ptr(E), nat.ptr(counts), B, n, shots, int(seed) & _M64, ctr0),
                   "qd_cpu_sample_z")
     return (E, counts) if return_counts else E
-
-
-class _QSimShotsHIP(torch.autograd.Function):
-    """Forward: the fused finite-shot kernel.  Backward: the exact adjoint (shot noise is straight-through)."""
-
-    @staticmethod
-    def forward(ctx, x, w, wgroup, shots, seed, ctr0, cptr):
-        B, n = x.shape
-        x = x.detach().float().contiguous()
-        w = w.detach().float().contiguous()
-        E = torch.empty(B, n, device=x.device, dtype=torch.float32)
-        if B > 0:
-            hip_qsim_shots_fwd(x, w, E, None, shots, seed, ctr0, cptr, wgroup)
-        ctx.save_for_backward(x, w)
-        return E
-
-    @staticmethod
-    def backward(ctx, gE):
-        dx, dw, _ = _QSimHIP.backward(ctx, gE)
-        return dx, dw, None, None, None, None, None
-
-
-class _QSimShotsCPU(torch.autograd.Function):
-    """Forward: simulate (fp64), then sample.  Backward: the exact adjoint (shot noise is straight-through)."""
-
-    @staticmethod
-    def forward(ctx, x, w, shots, seed, ctr0):
-        x = x.detach().float().contiguous()
-        w = w.detach().float().contiguous()
-        ctx.save_for_backward(x, w)
-        return sample_z(qsim_probs(x, w, "cpu"), shots, seed, ctr0)
-
-    @staticmethod
-    def backward(ctx, gE):
-        dx, dw = _QSimCPU.backward(ctx, gE)
-        return dx, dw, None, None, None
 
 
 class _ReplaceValue(torch.autograd.Function):
@@ -513,10 +495,13 @@ class NoiseModel:
         return "NoiseModel(" + ", ".join(f"{f}={getattr(self, f)!r}" for f in self.FIELDS) + ")"
 
 
-def _check_trajectories(shots: int, T) -> int:
+def _check_trajectories(T, shots: Optional[int] = None) -> int:
+    """T in range, and (with ``shots``) the shots split evenly over the trajectories."""
     T = int(T)
     if not 1 <= T <= MAX_TRAJECTORIES:
         raise ValueError(f"trajectories must be in 1..{MAX_TRAJECTORIES}, got {T}")
+    if shots is None:
+        return T
     if shots % T:
         raise ValueError(f"shots ({shots}) must be a multiple of trajectories ({T})")
     if T > 1 and (shots // T) % 4:
@@ -529,6 +514,16 @@ def _check_noise_shape(n: int, L: int) -> None:
         raise ValueError(f"the noise model supports 2 n L <= {MAX_NOISE_SITES} error sites, got n={n} L={L}")
 
 
+def _noise_qubit_limit(n: int) -> None:
+    if n > HIP_SHOTS_MAX_QUBITS:   # (the host oracles keep the kernels' range: one contract)
+        raise NotImplementedError(f"the noise model supports n <= {HIP_SHOTS_MAX_QUBITS} qubits, got {n}")
+
+
+def _check_noise_model(noise) -> None:
+    if not isinstance(noise, NoiseModel):
+        raise ValueError(f"noise must be a NoiseModel, got {type(noise).__name__}")
+
+
 @torch.no_grad()
 def noise_sites(noise: NoiseModel, B: int, n: int, L: int, T: int = 1, seed: int = 0, counter: int = 0,
                 device=None) -> torch.Tensor:
@@ -536,10 +531,8 @@ def noise_sites(noise: NoiseModel, B: int, n: int, L: int, T: int = 1, seed: int
     RZ.RY (0 none, 1 / 2 / 3 = X / Y / Z), [..., q, 1] after CNOT(q, q+1) (0 none, else 4 P_control + P_target).
     Drawn on the host by the C++ oracle of the kernel's contract."""
     _check_noise_shape(n, L)
-    if not 1 <= int(T) <= MAX_TRAJECTORIES:
-        raise ValueError(f"trajectories must be in 1..{MAX_TRAJECTORIES}, got {T}")
-    if n > HIP_SHOTS_MAX_QUBITS:
-        raise NotImplementedError(f"the noise model supports n <= {HIP_SHOTS_MAX_QUBITS} qubits, got {n}")
+    _check_trajectories(T)
+    _noise_qubit_limit(n)
     thr1, thr2, _ = noise.thresholds(n, "cpu")
     sites = torch.zeros(B, T, L, n, 2, dtype=torch.uint8)
     f = nat.fn(nat.cpu_lib(), "qd_cpu_noise_sites", [_p, _p, _p, _i, _i, _i, _i, _u64, _u64])
@@ -569,8 +562,7 @@ def _qsim_probs_framed(x: torch.Tensor, w: torch.Tensor, be: str, frames: torch.
     L = w.shape[-3]
     if be != "cpu":
         raise ValueError("qsim_probs(frames=) is the host oracle: backend 'cpu' only")
-    if x.device.type != "cpu":
-        raise RuntimeError("cpu backend needs CPU tensors")
+    _check_backend(be, x.device)
     if tuple(frames.shape) != (B, L, 2) or frames.dtype != torch.int32:
         raise ValueError(f"frames must be ({B}, {L}, 2) int32, got {tuple(frames.shape)} {frames.dtype}")
     _check_noise_shape(n, L)
@@ -597,7 +589,7 @@ def sample_z_noisy(probs: torch.Tensor, amask: torch.Tensor, noise: NoiseModel, 
     if probs.dim() != 3 or probs.shape[2] < 4 or probs.shape[2] & (probs.shape[2] - 1):
         raise ValueError(f"probs must be (B, T, 2^n) with n >= 2, got {tuple(probs.shape)}")
     B, T, n = probs.shape[0], probs.shape[1], probs.shape[2].bit_length() - 1
-    _check_trajectories(shots, T)
+    _check_trajectories(T, shots)
     if n > HIP_SHOTS_MAX_QUBITS:
         raise NotImplementedError(f"the shot samplers support n <= {HIP_SHOTS_MAX_QUBITS} qubits, got {n}")
     if tuple(amask.shape) != (B, T):
@@ -624,8 +616,7 @@ def hip_qsim_noisy_shots_fwd(x: torch.Tensor, w: torch.Tensor, E: torch.Tensor, 
     thr1, thr2, thr_ro = noise.thresholds(n, x.device)
     f = nat.fn(nat.hip_lib(), "qd_qsim_noisy_shots_fwd",
                [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _u64, _u64, _p, _p])
-    opt = lambda t: nat.ptr(t) if t is not None else None   # noqa: E731
-    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(E), opt(counts), opt(probs_out), opt(frames_out), nat.ptr(thr1),
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(E), _opt(counts), _opt(probs_out), _opt(frames_out), nat.ptr(thr1),
                 nat.ptr(thr2), nat.ptr(thr_ro), B, n, w.shape[-3], wgroup, shots, int(trajectories), seed & _M64,
                 ctr0 & _M64, counter_ptr, nat.stream_ptr(x.device)), "qd_qsim_noisy_shots_fwd")
 
@@ -653,53 +644,123 @@ def _noisy_shots_cpu(x, w, noise, shots, T, seed, ctr0) -> torch.Tensor:
     return sample_z_noisy(probs.view(B, T, 1 << n), frames[:, :, L - 1, 0], noise, shots, seed, ctr0)
 
 
-class _QSimNoisyHIP(torch.autograd.Function):
-    """Forward: the noisy finite-shot kernel.  Backward: the exact adjoint of the noiseless circuit (gate, readout
-    and shot noise are straight-through)."""
+# ----------------------------------------------------------------------------- the measurement mode
+DIFF_METHODS = ("adjoint", "parameter_shift", "on_chip", "noisy_adjoint")
+_MASK_METHODS = "shift_mask needs diff_method='parameter_shift' or 'on_chip'"
+
+
+@dataclasses.dataclass(frozen=True)
+class MeasureMode:
+    """The validated measurement arguments of a ``qsim`` call or a fused step: what ``resolve_measure`` returns
+    and the shared launchers (``hip_measured_fwd``, ``hip_measured_rows``) select their kernel by."""
+    diff_method: str = "adjoint"
+    shots: Optional[int] = None             # None: exact expectations
+    noise: Optional[NoiseModel] = None
+    trajectories: int = 1
+    masked: bool = False                    # a shift_mask was given
+
+
+def resolve_measure(diff_method, shots, noise, trajectories, shift_mask, n: int, L: int, be: str, device,
+                    mask_shape: bool = True) -> MeasureMode:
+    """The one place of the measurement arguments' rules (``qsim``'s docstring states them): the mode of a circuit
+    of ``n`` qubits and ``L`` layers on backend ``be`` with its tensors on ``device``, or the refusal -- first the
+    rules that hold on every backend, then what the backend and its kernels support.  ``mask_shape=False`` (the
+    fused step, whose mask is the kernel's flat one) leaves the shape of ``shift_mask`` to the caller.  The exact
+    mode (no shots, ``"adjoint"``) is every backend's: its caller checks the backend."""
+    if diff_method not in DIFF_METHODS:
+        raise ValueError(f"unknown diff_method {diff_method!r}: one of {DIFF_METHODS}")
+    pshift = diff_method in ("parameter_shift", "on_chip")
+    T = 1
+    if noise is not None:
+        _check_noise_model(noise)
+        if not shots:
+            raise ValueError("noise needs shots: the noise model is sampled per measurement shot")
+        if diff_method == "parameter_shift":
+            raise ValueError("noise with diff_method='parameter_shift' is not supported: "
+                             "diff_method='on_chip' measures the shifted circuits under the noise")
+        if shift_mask is not None and not pshift:
+            raise ValueError(_MASK_METHODS)
+        shots = _check_shots(shots)
+        T = _check_trajectories(trajectories, shots)
+    elif int(trajectories) != 1:
+        raise ValueError("trajectories needs noise")
+    if diff_method == "noisy_adjoint" and noise is None:
+        raise ValueError("diff_method='noisy_adjoint' needs noise= and shots=: it differentiates through the error "
+                         "gates the noisy shots forward samples")
+    if pshift:
+        if be == "torch":
+            raise ValueError("the torch backend has no parameter-shift rule; use hip or cpu")
+        _check_backend(be)
+        if diff_method == "on_chip" and not shots:
+            raise ValueError("diff_method='on_chip' needs shots: a device measures every circuit with finite shots")
+        if be == "hip" and device.type == "cuda":
+            _hip_shots_limit(n)
+        if 4 * n * L + 1 >= 1 << 16:
+            raise ValueError(f"parameter shift needs 2 * (2 n L) + 1 < 2^16 stream ids, got n={n} L={L}")
+        if shift_mask is not None and mask_shape and tuple(shift_mask.shape) != (L, n, 2):
+            raise ValueError(f"shift_mask must be {(L, n, 2)}, got {tuple(shift_mask.shape)}")
+        shots = _check_shots(shots) if shots else None
+        if noise is not None:
+            _check_noise_shape(n, L)
+        _check_backend(be, device)
+        return MeasureMode(diff_method, shots, noise, T, shift_mask is not None)
+    if shift_mask is not None:
+        raise ValueError(_MASK_METHODS)
+    shots = _check_shots(shots) if shots else None
+    if shots is not None:
+        if be == "torch":
+            raise ValueError("the torch backend has no noise model; use hip or cpu" if noise is not None else
+                             "the torch backend has no finite-shot sampler; use hip or cpu")
+        _check_backend(be, device)
+        if be == "hip":
+            _hip_shots_limit(n)
+        if noise is not None:
+            _check_noise_shape(n, L)
+    return MeasureMode(diff_method, shots, noise, T, False)
+
+
+def hip_measured_fwd(x: torch.Tensor, w: torch.Tensor, E: torch.Tensor, mode: MeasureMode, seed: int = 0,
+                     ctr0: int = 0, counter_ptr=None, wgroup: int = 0) -> None:
+    """The measured forward of a mode with shots, E (B, n) fp32: the noisy kernel under ``mode.noise``, else the
+    fused finite-shot one.  ``qsim`` and the fused step (ops/qsc.py) both launch through here."""
+    if mode.noise is not None:
+        hip_qsim_noisy_shots_fwd(x, w, E, None, mode.noise, mode.shots, mode.trajectories, seed, ctr0, counter_ptr,
+                                 wgroup)
+    else:
+        hip_qsim_shots_fwd(x, w, E, None, mode.shots, seed, ctr0, counter_ptr, wgroup)
+
+
+@torch.no_grad()
+def _measured_fwd(x, w, be, mode: MeasureMode, seed, ctr0, cptr=None) -> torch.Tensor:
+    """E (B, n) fp32 of a mode with shots on ``hip`` or ``cpu``; x, w fp32 contiguous."""
+    if be == "hip":
+        E = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+        if x.shape[0] > 0:
+            hip_measured_fwd(x, w, E, mode, seed, ctr0, cptr, wgroup_of(x, w))
+        return E
+    if mode.noise is not None:
+        return _noisy_shots_cpu(x, w, mode.noise, mode.shots, mode.trajectories, seed, ctr0)
+    return sample_z(qsim_probs(x, w, "cpu"), mode.shots, seed, ctr0)
+
+
+class _QSimMeasuredHIP(torch.autograd.Function):
+    """Forward: the finite-shot kernel, noisy or not.  Backward: the exact adjoint of the noiseless circuit (gate,
+    readout and shot noise are straight-through)."""
 
     @staticmethod
-    def forward(ctx, x, w, wgroup, noise, shots, T, seed, ctr0, cptr):
-        B, n = x.shape
+    def forward(ctx, x, w, mode, seed, ctr0, cptr):
         x = x.detach().float().contiguous()
         w = w.detach().float().contiguous()
-        E = torch.empty(B, n, device=x.device, dtype=torch.float32)
-        if B > 0:
-            hip_qsim_noisy_shots_fwd(x, w, E, None, noise, shots, T, seed, ctr0, cptr, wgroup)
         ctx.save_for_backward(x, w)
-        return E
+        return _measured_fwd(x, w, "hip", mode, seed, ctr0, cptr)
 
     @staticmethod
     def backward(ctx, gE):
         dx, dw, _ = _QSimHIP.backward(ctx, gE)
-        return dx, dw, None, None, None, None, None, None, None
-
-
-def _qsim_noisy(x, w, be, noise, shots, T, seed, counter) -> torch.Tensor:
-    n, L = x.shape[1], w.shape[-3]
-    if be == "torch":
-        raise ValueError("the torch backend has no noise model; use hip or cpu")
-    if be == "hip":
-        if x.device.type != "cuda":
-            raise RuntimeError("hip backend needs CUDA/HIP tensors")
-        _hip_shots_limit(n)
-        _check_noise_shape(n, L)
-        if 2 * n * L > 256 and n > HIP_REG_MAX_QUBITS:   # (the adjoint's limit, as for the exact call)
-            raise NotImplementedError("large-n HIP simulator supports 2*n*L <= 256")
-        ctr0, cptr = _split_counter(counter, x.device)
-        return _QSimNoisyHIP.apply(x, w, wgroup_of(x, w), noise, shots, T, int(seed), ctr0, cptr)
-    if be == "cpu":
-        if x.device.type != "cpu":
-            raise RuntimeError("cpu backend needs CPU tensors")
-        _check_noise_shape(n, L)
-        ctr0, _ = _split_counter(counter, x.device)
-        E = _noisy_shots_cpu(x.detach().float().contiguous(), w.detach().float().contiguous(), noise, shots, T,
-                             int(seed), ctr0)
-        return _ReplaceValue.apply(qsim(x, w, "cpu"), E)
-    raise ValueError(f"unknown backend {be!r}")
+        return dx, dw, None, None, None, None
 
 
 # ----------------------------------------------------------------------------- parameter shift
-DIFF_METHODS = ("adjoint", "parameter_shift", "on_chip", "noisy_adjoint")
 PSHIFT_ID_SHIFT = 48   # circuit (p, s) draws under call counter c + (id << 48), id = 1 + 2p + s; the forward is id 0
 
 
@@ -709,16 +770,10 @@ def pshift_counter(counter: int, p: int, s: int) -> int:
     return (int(counter) + ((1 + 2 * p + s) << PSHIFT_ID_SHIFT)) & _M64
 
 
-def _check_pshift_shape(n: int, L: int) -> None:
-    if 4 * n * L + 1 >= 1 << 16:
-        raise ValueError(f"parameter shift needs 2 * (2 n L) + 1 < 2^16 stream ids, got n={n} L={L}")
-
-
 def _mask_u8(shift_mask, w: torch.Tensor) -> Optional[torch.Tensor]:
+    """The kernels' flat (2nL) uint8 mask of an (L, n, 2) ``shift_mask`` (its shape: ``resolve_measure``)."""
     if shift_mask is None:
         return None
-    if tuple(shift_mask.shape) != tuple(w.shape[-3:]):
-        raise ValueError(f"shift_mask must be {tuple(w.shape[-3:])}, got {tuple(shift_mask.shape)}")
     return (shift_mask != 0).to(device=w.device, dtype=torch.uint8).reshape(-1).contiguous()
 
 
@@ -733,8 +788,7 @@ def hip_qsim_pshift(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, G: torch
     B, n = x.shape
     f = nat.fn(nat.hip_lib(), "qd_qsim_pshift",
                [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _u64, _u64, _p, _p])
-    opt = lambda t: nat.ptr(t) if t is not None else None   # noqa: E731
-    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(gE), nat.ptr(G), opt(Epm), opt(probs), opt(mask), B, n, w.shape[-3],
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(gE), nat.ptr(G), _opt(Epm), _opt(probs), _opt(mask), B, n, w.shape[-3],
                 wgroup, int(need_dx), shots, seed & _M64, ctr0 & _M64, counter_ptr, nat.stream_ptr(x.device)),
               "qd_qsim_pshift")
 
@@ -751,8 +805,7 @@ def hip_qsim_noisy_pshift(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, G:
     thr1, thr2, thr_ro = (noise if noise is not None else NoiseModel()).thresholds(n, x.device)
     f = nat.fn(nat.hip_lib(), "qd_qsim_noisy_pshift",
                [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _u64, _u64, _p, _p])
-    opt = lambda t: nat.ptr(t) if t is not None else None   # noqa: E731
-    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(gE), nat.ptr(G), opt(Epm), opt(probs), opt(frames), opt(mask),
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(gE), nat.ptr(G), _opt(Epm), _opt(probs), _opt(frames), _opt(mask),
                 nat.ptr(thr1), nat.ptr(thr2), nat.ptr(thr_ro), B, n, w.shape[-3], wgroup, int(need_dx), shots,
                 int(trajectories), seed & _M64, ctr0 & _M64, counter_ptr, nat.stream_ptr(x.device)),
               "qd_qsim_noisy_pshift")
@@ -793,42 +846,53 @@ def pshift_rows(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, backend: Opt
     readout fields drawn under the circuit's own counter -- csrc/hip/qsim_onchip.hip."""
     _check_shapes(x, w)
     B, n = x.shape
-    _check_pshift_shape(n, w.shape[-3])
-    shots = _check_shots(shots) if shots else 0
-    if noise is not None:
-        if not isinstance(noise, NoiseModel):
-            raise ValueError(f"noise must be a NoiseModel, got {type(noise).__name__}")
-        if not shots:
-            raise ValueError("noise needs shots: the noise model is sampled per measurement shot")
-        trajectories = _check_trajectories(shots, trajectories)
-        _check_noise_shape(n, w.shape[-3])
-    elif int(trajectories) != 1:
-        raise ValueError("trajectories needs noise")
     be = backend if backend not in (None, "auto") else default_backend(x.device)
+    mode = resolve_measure("on_chip" if noise is not None else "parameter_shift", shots, noise, trajectories,
+                           shift_mask, n, w.shape[-3], be, x.device)
     x = x.detach().float().contiguous()
     w = w.detach().float().contiguous()
     gE = gE.detach().float().contiguous()
     mask = _mask_u8(shift_mask, w)
-    if be == "hip":
-        if x.device.type != "cuda":
-            raise RuntimeError("hip backend needs CUDA/HIP tensors")
-        _hip_shots_limit(n)
-        ctr0, cptr = _split_counter(counter, x.device)
-        G = torch.empty(B, 2 * n * w.shape[-3], device=x.device, dtype=torch.float32)
-        if B > 0 and noise is not None:
-            hip_qsim_noisy_pshift(x, w, gE, G, None, None, mask, need_dx, shots, int(seed), ctr0, cptr,
-                                  wgroup_of(x, w), noise, trajectories)
-        elif B > 0:
-            hip_qsim_pshift(x, w, gE, G, None, None, mask, need_dx, shots, int(seed), ctr0, cptr, wgroup_of(x, w))
-        return G
+    ctr0, cptr = split_counter(counter, x.device)
     if be == "cpu":
-        if x.device.type != "cpu":
-            raise RuntimeError("cpu backend needs CPU tensors")
-        ctr0, _ = _split_counter(counter, x.device)
-        return _pshift_rows_cpu(x, w, gE, mask, need_dx, shots, int(seed), ctr0, noise, trajectories)
-    if be == "torch":
-        raise ValueError("the torch backend has no parameter-shift rule; use hip or cpu")
-    raise ValueError(f"unknown backend {be!r}")
+        return _pshift_rows_cpu(x, w, gE, mask, need_dx, mode.shots or 0, int(seed), ctr0, noise, mode.trajectories)
+    G = torch.empty(B, 2 * n * w.shape[-3], device=x.device, dtype=torch.float32)
+    if B > 0:
+        hip_measured_rows(x, w, gE, G, mode, mask, int(seed), ctr0, cptr, wgroup_of(x, w), need_dx)
+    return G
+
+
+def hip_measured_rows(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, G: torch.Tensor, mode: MeasureMode,
+                      mask: Optional[torch.Tensor] = None, seed: int = 0, ctr0: int = 0, counter_ptr=None,
+                      wgroup: int = 0, need_dx: bool = True, Ebar: Optional[torch.Tensor] = None) -> None:
+    """The per-sample gradient rows G (B, 2nL) fp32 of a mode's own backward: the noise-aware adjoint
+    (``Ebar``: nullable, its expectation), else the parameter-shift rule under ``mode.noise`` or without
+    (``mask``: nullable, the flat uint8 one).  ``qsim``'s rows functions and the fused step (ops/qsc.py) both launch
+    through here."""
+    if mode.diff_method == "noisy_adjoint":
+        hip_qsim_noisy_adjoint(x, w, gE, G, mode.noise, mode.trajectories, seed, ctr0, counter_ptr, wgroup, Ebar)
+    elif mode.noise is not None:
+        hip_qsim_noisy_pshift(x, w, gE, G, None, None, mask, need_dx, mode.shots, seed, ctr0, counter_ptr, wgroup,
+                              mode.noise, mode.trajectories)
+    else:
+        hip_qsim_pshift(x, w, gE, G, None, None, mask, need_dx, mode.shots or 0, seed, ctr0, counter_ptr, wgroup)
+
+
+def _rows_to_grads(G: torch.Tensor, x: torch.Tensor, w: torch.Tensor, be: str, shift_mask=None):
+    """(dx, dw) of the gradient rows G (B, 2nL): dx its layer-0 RY columns, dw its sum over the samples."""
+    B, n = x.shape
+    L = w.shape[-3]
+    dx = G[:, 0:2 * n:2].contiguous()
+    if be == "hip" and B > 0:   # deterministic: no float atomics
+        dw = reduce_slab(G, torch.empty(2 * n * L, device=x.device, dtype=torch.float32))
+    else:
+        dw = G.sum(0)
+    if shift_mask is not None:   # (a masked layer-0 RY column still carries dx)
+        dw = dw * _mask_u8(shift_mask, w)
+    dw = dw.view(L, n, 2)
+    if w.dim() == 4:
+        dw = _group_grad(dw, w)
+    return dx, dw
 
 
 class _QSimPShift(torch.autograd.Function):
@@ -837,35 +901,21 @@ class _QSimPShift(torch.autograd.Function):
     backward)."""
 
     @staticmethod
-    def forward(ctx, x, w, be, shots, seed, counter, shift_mask, noise=None, T=1):
+    def forward(ctx, x, w, be, mode, seed, counter, shift_mask):
         x = x.detach().float().contiguous()
         w = w.detach().float().contiguous()
         ctx.save_for_backward(x, w)
-        ctx.args = (be, shots, seed, counter, shift_mask, noise, T)
-        return qsim(x, w, be, shots=shots, seed=seed, counter=counter, noise=noise, trajectories=T)
+        ctx.args = (be, mode, seed, counter, shift_mask)
+        return qsim(x, w, be, shots=mode.shots, seed=seed, counter=counter, noise=mode.noise,
+                    trajectories=mode.trajectories)
 
     @staticmethod
     def backward(ctx, gE):
         x, w = ctx.saved_tensors
-        be, shots, seed, counter, shift_mask, noise, T = ctx.args
-        B, n = x.shape
-        L = w.shape[-3]
-        P = 2 * n * L
-        G = pshift_rows(x, w, gE, be, shots, seed, counter, shift_mask, need_dx=ctx.needs_input_grad[0], noise=noise,
-                        trajectories=T)
-        dx = G[:, 0:2 * n:2].contiguous()
-        if be == "hip" and B > 0:   # deterministic: no float atomics
-            dw = torch.empty(P, device=x.device, dtype=torch.float32)
-            r = nat.fn(nat.hip_lib(), "qd_reduce_slab", [_p, _p, _i, _i, _f, _p])
-            nat.check(r(nat.ptr(G), nat.ptr(dw), B, P, 0.0, nat.stream_ptr(x.device)), "qd_reduce_slab")
-        else:
-            dw = G.sum(0)
-        if shift_mask is not None:   # (a masked layer-0 RY column still carries dx)
-            dw = dw * _mask_u8(shift_mask, w)
-        dw = dw.view(L, n, 2)
-        if w.dim() == 4:
-            dw = _group_grad(dw, w)
-        return dx, dw, None, None, None, None, None, None, None
+        be, mode, seed, counter, shift_mask = ctx.args
+        G = pshift_rows(x, w, gE, be, mode.shots, seed, counter, shift_mask, need_dx=ctx.needs_input_grad[0],
+                        noise=mode.noise, trajectories=mode.trajectories)
+        return _rows_to_grads(G, x, w, be, shift_mask) + (None,) * 5
 
 
 # ----------------------------------------------------------------------------- noise-aware adjoint
@@ -889,8 +939,7 @@ def hip_qsim_noisy_adjoint(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, G
     work = torch.empty(split * B * (2 * n * L + n), device=x.device, dtype=torch.float32) if split > 1 else None
     f = nat.fn(nat.hip_lib(), "qd_qsim_noisy_adjoint",
                [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _u64, _u64, _p, _p])
-    opt = lambda t: nat.ptr(t) if t is not None else None   # noqa: E731
-    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(gE), nat.ptr(G), opt(Ebar), opt(frames), opt(work), nat.ptr(thr1),
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(gE), nat.ptr(G), _opt(Ebar), _opt(frames), _opt(work), nat.ptr(thr1),
                 nat.ptr(thr2), nat.ptr(thr_ro), B, n, L, wgroup, T, seed & _M64, ctr0 & _M64, counter_ptr,
                 nat.stream_ptr(x.device)), "qd_qsim_noisy_adjoint")
 
@@ -946,11 +995,8 @@ def noisy_adjoint_rows(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, noise
     _check_shapes(x, w)
     B, n = x.shape
     L = w.shape[-3]
-    if not isinstance(noise, NoiseModel):
-        raise ValueError(f"noise must be a NoiseModel, got {type(noise).__name__}")
-    T = int(trajectories)
-    if not 1 <= T <= MAX_TRAJECTORIES:
-        raise ValueError(f"trajectories must be in 1..{MAX_TRAJECTORIES}, got {T}")
+    _check_noise_model(noise)
+    T = _check_trajectories(trajectories)
     _check_noise_shape(n, L)
     be = backend if backend not in (None, "auto") else default_backend(x.device)
     x = x.detach().float().contiguous()
@@ -958,27 +1004,22 @@ def noisy_adjoint_rows(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, noise
     gE = gE.detach().float().contiguous()
     if tuple(gE.shape) != (B, n):
         raise ValueError(f"gE must be ({B}, {n}), got {tuple(gE.shape)}")
-    if be == "hip":
-        if x.device.type != "cuda":
-            raise RuntimeError("hip backend needs CUDA/HIP tensors")
-        _hip_shots_limit(n)
-        ctr0, cptr = _split_counter(counter, x.device)
-        G = torch.empty(B, 2 * n * L, device=x.device, dtype=torch.float32)
-        Ebar = torch.empty(B, n, device=x.device, dtype=torch.float32) if return_expectation else None
-        if B > 0:
-            hip_qsim_noisy_adjoint(x, w, gE, G, noise, T, int(seed), ctr0, cptr, wgroup_of(x, w), Ebar)
-        return (G, Ebar) if return_expectation else G
-    if be == "cpu":
-        if x.device.type != "cpu":
-            raise RuntimeError("cpu backend needs CPU tensors")
-        if n > HIP_SHOTS_MAX_QUBITS:
-            raise NotImplementedError(f"the noise model supports n <= {HIP_SHOTS_MAX_QUBITS} qubits, got {n}")
-        ctr0, _ = _split_counter(counter, x.device)
-        G, Ebar = _nadj_rows_cpu(x, w, gE, noise, T, int(seed), ctr0)
-        return (G, Ebar) if return_expectation else G
     if be == "torch":
         raise ValueError("the torch backend has no noise model; use hip or cpu")
-    raise ValueError(f"unknown backend {be!r}")
+    _check_backend(be, x.device)
+    if be == "hip":
+        _hip_shots_limit(n)
+        ctr0, cptr = split_counter(counter, x.device)
+        G = torch.empty(B, 2 * n * L, device=x.device, dtype=torch.float32)
+        Ebar = torch.empty(B, n, device=x.device, dtype=torch.float32) if return_expectation else None
+        if B > 0:   # (the rows need no shots: the mode is this function's own)
+            hip_measured_rows(x, w, gE, G, MeasureMode("noisy_adjoint", None, noise, T), None, int(seed), ctr0, cptr,
+                              wgroup_of(x, w), Ebar=Ebar)
+    else:
+        _noise_qubit_limit(n)
+        ctr0, _ = split_counter(counter, x.device)
+        G, Ebar = _nadj_rows_cpu(x, w, gE, noise, T, int(seed), ctr0)
+    return (G, Ebar) if return_expectation else G
 
 
 class _QSimNoisyAdjoint(torch.autograd.Function):
@@ -987,89 +1028,27 @@ class _QSimNoisyAdjoint(torch.autograd.Function):
     advance it after the backward)."""
 
     @staticmethod
-    def forward(ctx, x, w, be, noise, shots, T, seed, counter):
-        B, n = x.shape
+    def forward(ctx, x, w, be, mode, seed, counter):
         x = x.detach().float().contiguous()
         w = w.detach().float().contiguous()
         ctx.save_for_backward(x, w)
-        ctx.args = (be, noise, T, seed, counter)
-        ctr0, cptr = _split_counter(counter, x.device)
-        if be == "hip":
-            E = torch.empty(B, n, device=x.device, dtype=torch.float32)
-            if B > 0:
-                hip_qsim_noisy_shots_fwd(x, w, E, None, noise, shots, T, seed, ctr0, cptr, wgroup_of(x, w))
-            return E
-        return _noisy_shots_cpu(x, w, noise, shots, T, seed, ctr0)
+        ctx.args = (be, mode, seed, counter)
+        return _measured_fwd(x, w, be, mode, seed, *split_counter(counter, x.device))
 
     @staticmethod
     def backward(ctx, gE):
         x, w = ctx.saved_tensors
-        be, noise, T, seed, counter = ctx.args
-        B, n = x.shape
-        L = w.shape[-3]
-        P = 2 * n * L
-        G = noisy_adjoint_rows(x, w, gE, noise, T, seed, counter, be)
-        dx = G[:, 0:2 * n:2].contiguous()
-        if be == "hip" and B > 0:   # deterministic: no float atomics
-            dw = torch.empty(P, device=x.device, dtype=torch.float32)
-            r = nat.fn(nat.hip_lib(), "qd_reduce_slab", [_p, _p, _i, _i, _f, _p])
-            nat.check(r(nat.ptr(G), nat.ptr(dw), B, P, 0.0, nat.stream_ptr(x.device)), "qd_reduce_slab")
-        else:
-            dw = G.sum(0)
-        dw = dw.view(L, n, 2)
-        if w.dim() == 4:
-            dw = _group_grad(dw, w)
-        return dx, dw, None, None, None, None, None, None
+        be, mode, seed, counter = ctx.args
+        G = noisy_adjoint_rows(x, w, gE, mode.noise, mode.trajectories, seed, counter, be)
+        return _rows_to_grads(G, x, w, be) + (None,) * 4
 
 
-def _qsim_noisy_adjoint(x, w, be, noise, shots, T, seed, counter) -> torch.Tensor:
-    n, L = x.shape[1], w.shape[-3]
-    if be == "torch":
-        raise ValueError("the torch backend has no noise model; use hip or cpu")
-    if be not in ("hip", "cpu"):
-        raise ValueError(f"unknown backend {be!r}")
-    if x.device.type != ("cuda" if be == "hip" else "cpu"):
-        raise RuntimeError("hip backend needs CUDA/HIP tensors" if be == "hip" else "cpu backend needs CPU tensors")
-    if be == "hip":
-        _hip_shots_limit(n)
-    _check_noise_shape(n, L)
-    return _QSimNoisyAdjoint.apply(x, w, be, noise, shots, T, int(seed), counter)
-
-
-def _check_measure_args(diff_method, shots, noise, trajectories, shift_mask):
-    """The combination rules of ``qsim``'s measurement arguments that hold on every backend (``qsim`` and the fused
-    step, ops/qsc.py, share them): (shots, trajectories), both checked when ``noise`` is set."""
-    if diff_method not in DIFF_METHODS:
-        raise ValueError(f"unknown diff_method {diff_method!r}: one of {DIFF_METHODS}")
-    T = 1
-    if noise is not None:
-        if not isinstance(noise, NoiseModel):
-            raise ValueError(f"noise must be a NoiseModel, got {type(noise).__name__}")
-        if not shots:
-            raise ValueError("noise needs shots: the noise model is sampled per measurement shot")
-        if diff_method == "parameter_shift":
-            raise ValueError("noise with diff_method='parameter_shift' is not supported: "
-                             "diff_method='on_chip' measures the shifted circuits under the noise")
-        if shift_mask is not None and diff_method != "on_chip":
-            raise ValueError("shift_mask needs diff_method='parameter_shift' or 'on_chip'")
-        shots = _check_shots(shots)
-        T = _check_trajectories(shots, trajectories)
-    elif int(trajectories) != 1:
-        raise ValueError("trajectories needs noise")
-    if diff_method == "noisy_adjoint" and noise is None:
-        raise ValueError("diff_method='noisy_adjoint' needs noise= and shots=: it differentiates through the error "
-                         "gates the noisy shots forward samples")
-    return shots, T
-
-
-def _check_on_chip_shots(diff_method, shots) -> None:
-    if diff_method == "on_chip" and not shots:
-        raise ValueError("diff_method='on_chip' needs shots: a device measures every circuit with finite shots")
-
-
-def _check_mask_method(diff_method, shift_mask) -> None:
-    if shift_mask is not None and diff_method not in ("parameter_shift", "on_chip"):
-        raise ValueError("shift_mask needs diff_method='parameter_shift' or 'on_chip'")
+def _check_hip_adjoint(n: int, L: int) -> None:
+    """What the exact HIP simulators run: the forward of the exact mode, the backward of the straight-through ones."""
+    if n > HIP_MAX_QUBITS:
+        raise NotImplementedError(f"HIP simulators support n <= {HIP_MAX_QUBITS}")
+    if 2 * n * L > 256 and n > HIP_REG_MAX_QUBITS:
+        raise NotImplementedError("large-n HIP simulator supports 2*n*L <= 256")
 
 
 def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots: Optional[int] = None, seed: int = 0,
@@ -1117,69 +1096,27 @@ def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots:
     passes per sample.  A device ``counter`` is read again by the backward: advance it after the backward.
     ``shift_mask`` is not available."""
     _check_shapes(x, w)
-    n = x.shape[1]
+    n, L = x.shape[1], w.shape[-3]
     be = backend if backend not in (None, "auto") else default_backend(x.device)
-    shots, T = _check_measure_args(diff_method, shots, noise, trajectories, shift_mask)
-    if noise is not None and diff_method == "adjoint":
-        return _qsim_noisy(x, w, be, noise, shots, T, seed, counter)
-    if noise is not None and diff_method == "noisy_adjoint":
-        return _qsim_noisy_adjoint(x, w, be, noise, shots, T, seed, counter)
-    if diff_method in ("parameter_shift", "on_chip"):
-        if be == "torch":
-            raise ValueError("the torch backend has no parameter-shift rule; use hip or cpu")
-        if be not in ("hip", "cpu"):
-            raise ValueError(f"unknown backend {be!r}")
-        _check_on_chip_shots(diff_method, shots)
-        if be == "hip" and x.device.type == "cuda":
-            _hip_shots_limit(n)
-        _check_pshift_shape(n, w.shape[-3])
-        _mask_u8(shift_mask, w)
-        shots = _check_shots(shots) if shots else None
-        if noise is None:
-            return _QSimPShift.apply(x, w, be, shots, int(seed), counter, shift_mask)
-        _check_noise_shape(n, w.shape[-3])
-        return _QSimPShift.apply(x, w, be, shots, int(seed), counter, shift_mask, noise, T)
-    _check_mask_method(diff_method, shift_mask)
-    if shots:
-        shots = _check_shots(shots)
-        if be == "torch":
-            raise ValueError("the torch backend has no finite-shot sampler; use hip or cpu")
-        if be == "hip":
-            if x.device.type != "cuda":
-                raise RuntimeError("hip backend needs CUDA/HIP tensors")
-            _hip_shots_limit(n)
-            if 2 * n * w.shape[-3] > 256 and n > HIP_REG_MAX_QUBITS:   # (the adjoint's limit, as for the exact call)
-                raise NotImplementedError("large-n HIP simulator supports 2*n*L <= 256")
-            ctr0, cptr = _split_counter(counter, x.device)
-            return _QSimShotsHIP.apply(x, w, wgroup_of(x, w), shots, int(seed), ctr0, cptr)
-        if be == "cpu":
-            if x.device.type != "cpu":
-                raise RuntimeError("cpu backend needs CPU tensors")
-            ctr0, _ = _split_counter(counter, x.device)
-            if w.dim() == 4:  # exact per-group forward for the graph, its values replaced by the sampled ones
-                E = sample_z(qsim_probs(x, w, "cpu"), shots, int(seed), ctr0)
-                return _ReplaceValue.apply(qsim(x, w, "cpu"), E)
-            return _QSimShotsCPU.apply(x, w, shots, int(seed), ctr0)
-        raise ValueError(f"unknown backend {be!r}")
+    mode = resolve_measure(diff_method, shots, noise, trajectories, shift_mask, n, L, be, x.device)
+    if mode.diff_method == "noisy_adjoint":
+        return _QSimNoisyAdjoint.apply(x, w, be, mode, int(seed), counter)
+    if mode.diff_method != "adjoint":   # the parameter-shift family
+        return _QSimPShift.apply(x, w, be, mode, int(seed), counter, shift_mask)
+    if mode.shots and be == "hip":   # straight-through: the measured forward, the exact adjoint's backward
+        _check_hip_adjoint(n, L)
+        return _QSimMeasuredHIP.apply(x, w, mode, int(seed), *split_counter(counter, x.device))
+    if mode.shots:   # the exact forward for the graph, its values replaced by the measured ones
+        ctr0, _ = split_counter(counter, x.device)
+        E = _measured_fwd(x.detach().float().contiguous(), w.detach().float().contiguous(), be, mode, int(seed), ctr0)
+        return _ReplaceValue.apply(qsim(x, w, "cpu"), E)
+    _check_backend(be, x.device)
     if be == "hip":
-        if x.device.type != "cuda":
-            raise RuntimeError("hip backend needs CUDA/HIP tensors")
-        if n > HIP_MAX_QUBITS:
-            raise NotImplementedError(f"HIP simulators support n <= {HIP_MAX_QUBITS}")
-        if 2 * n * w.shape[-3] > 256 and n > HIP_REG_MAX_QUBITS:
-            raise NotImplementedError("large-n HIP simulator supports 2*n*L <= 256")
-        wgroup = x.shape[0] // w.shape[0] if w.dim() == 4 else 0
-        return _QSimHIP.apply(x, w, wgroup)
+        _check_hip_adjoint(n, L)
+        return _QSimHIP.apply(x, w, wgroup_of(x, w))
     if w.dim() == 4:  # host backends: run per group
-        G = w.shape[0]
-        return torch.cat([qsim(xc, w[g], be) for g, xc in enumerate(x.chunk(G))], dim=0)
-    if be == "cpu":
-        if x.device.type != "cpu":
-            raise RuntimeError("cpu backend needs CPU tensors")
-        return _QSimCPU.apply(x, w)
-    if be == "torch":
-        return qsim_torch(x, w)
-    raise ValueError(f"unknown backend {be!r}")
+        return torch.cat([qsim(xc, w[g], be) for g, xc in enumerate(x.chunk(w.shape[0]))], dim=0)
+    return _QSimCPU.apply(x, w) if be == "cpu" else qsim_torch(x, w)
 
 
 def init_weights_(w: torch.Tensor, generator: Optional[torch.Generator] = None) -> torch.Tensor:

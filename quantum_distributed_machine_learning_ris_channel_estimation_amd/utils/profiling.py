@@ -75,6 +75,72 @@ class EventTimer:
         return {k: sum(s.elapsed_time(e) for s, e in v) / len(v) for k, v in self.events.items()}
 
 
+# ---- the timing scripts' shared loop (scripts/*_timing.py): variants captured as graphs, timed in alternation
+def graph_of(run: Callable[[], None], iters: int = 1, warm: int = 0) -> "torch.cuda.CUDAGraph":
+    """``iters`` back-to-back calls of ``run`` captured as one HIP graph (so the host's launch rate is not what is
+    timed), after ``warm`` eager calls on a side stream."""
+    if warm:
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warm):
+                run()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(iters):
+            run()
+    return g
+
+
+def timed(fn: Callable[[], None], iters: int = 1) -> float:
+    """Milliseconds per call of ``fn``, ``iters`` calls between two events."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def alternate(fns: Dict[str, Callable[[], None]], rounds: int, iters: int = 1, scale: float = 1.0) -> Dict[str, List[float]]:
+    """{variant: [ms per call x ``scale``, one per round]}: two warm-up calls of every variant, then ``rounds``
+    rounds in which the variants alternate, each timed over ``iters`` calls."""
+    for f in fns.values():
+        f()
+        f()
+    torch.cuda.synchronize()
+    times: Dict[str, List[float]] = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, f in fns.items():
+            times[k].append(timed(f, iters) * scale)
+    return times
+
+
+def time_graphed(fns: Dict[str, Callable[[], None]], iters: int, rounds: int) -> Dict[str, List[float]]:
+    """{variant: [microseconds per repetition, one per round]}, every variant a graph of ``iters`` repetitions."""
+    graphs = {k: graph_of(f, iters) for k, f in fns.items()}
+    return alternate({k: g.replay for k, g in graphs.items()}, rounds, 1, 1e3 / iters)
+
+
+def cell(v: Sequence[float], width: int = 9, prec: int = 1, scale: float = 1.0) -> str:
+    """A table cell: median (min .. max)."""
+    import statistics
+    return f"{statistics.median(v) * scale:{width}.{prec}f} ({min(v) * scale:.{prec}f} .. {max(v) * scale:.{prec}f})"
+
+
+def write_report(lines: Sequence[str], out: Optional[str]) -> None:
+    """Print the report, and write it to ``out`` if that is given."""
+    text = "\n".join(lines)
+    print(text)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text + "\n")
+
+
 _GRAVEYARD: list = []   # graph executables of closed / dropped GraphedSteps, destroyed at exit (or a safe point)
 # When a parked executable is destroyed.  "exit" (default): at interpreter exit only.  Round 6's native crash
 # report (profiles/r6_11b_bench_forced_segfault.txt) put the recurring host segfault of hipGraphLaunch (rounds 5

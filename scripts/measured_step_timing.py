@@ -29,6 +29,8 @@ from quantum_distributed_machine_learning_ris_channel_estimation_amd.ops.optim i
 from quantum_distributed_machine_learning_ris_channel_estimation_amd.ops.qoc import QOCPruner  # noqa: E402
 from quantum_distributed_machine_learning_ris_channel_estimation_amd.ops.quantum import NoiseModel  # noqa: E402
 from quantum_distributed_machine_learning_ris_channel_estimation_amd.train.engine import ClassifierStep  # noqa: E402
+from quantum_distributed_machine_learning_ris_channel_estimation_amd.utils.profiling import (alternate, cell, graph_of,  # noqa: E402
+                                                                                             timed, write_report)
 
 N, L, T, SHOTS, SEED = 8, 3, 64, 1024, 1234
 NOISE = NoiseModel(1e-3, 1e-2, 0.02, 0.02)
@@ -64,53 +66,17 @@ def world(dev, streams, per_stream, diff_method, fused, prune_ratio=None):
     return run, pruner
 
 
-def graph_of(run):
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        for _ in range(3):
-            run()
-    torch.cuda.current_stream().wait_stream(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        run()
-    return g
-
-
-def timed(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def cell(v):
-    return f"{statistics.median(v):9.3f} ({min(v):.3f} .. {max(v):.3f})"
-
-
 def part_a(dev, rounds, iters, lines):
     lines.append(f"(a) whole step, 9 x 256 samples, n = {N}, L = {L}, T = {T}, {SHOTS} shots, noise point; ms per step")
     lines.append(f"{'diff_method':>14}  {'fused + graphed':>30}  {'module path (eager)':>30}  module/fused  ranges apart")
     for dm in ("noisy_adjoint", "adjoint"):
         fused, _ = world(dev, 9, 256, dm, True)
         module, _ = world(dev, 9, 256, dm, False)
-        g = graph_of(fused)
-        fns = {"fused": g.replay, "module": module}
-        for f in fns.values():   # warm-up
-            f()
-            f()
-        torch.cuda.synchronize()
-        times = {k: [] for k in fns}
-        for _ in range(rounds):
-            for k, f in fns.items():
-                times[k].append(timed(f, iters))
+        g = graph_of(fused, warm=3)
+        times = alternate({"fused": g.replay, "module": module}, rounds, iters)
         ratio = statistics.median(times["module"]) / statistics.median(times["fused"])
         apart = "yes" if max(times["fused"]) < min(times["module"]) else "NO"
-        lines.append(f"{dm:>14}  {cell(times['fused']):>30}  {cell(times['module']):>30}  {ratio:>12.2f}  {apart:>12}")
+        lines.append(f"{dm:>14}  {cell(times['fused'], 9, 3):>30}  {cell(times['module'], 9, 3):>30}  {ratio:>12.2f}  {apart:>12}")
         print(lines[-1], flush=True)
 
 
@@ -128,7 +94,7 @@ def part_b(dev, rounds, periods, lines, streams=1):
     lines.append(f"{'ratio':>6}  {'all steps':>30}  {'accumulating steps':>30}  {'pruned steps':>30}  "
                  f"mean circuits  circuits in pruned steps")
     worlds = {r: world(dev, streams, 256, "on_chip", True, prune_ratio=r) for r in (0.0, 0.5)}
-    graphs = {r: graph_of(run) for r, (run, _) in worlds.items()}
+    graphs = {r: graph_of(run, warm=3) for r, (run, _) in worlds.items()}
     for r, (_, pr) in worlds.items():   # the schedule from step 0, whatever warm-up and capture left
         pr.acc.zero_()
         pr.mask.fill_(1)
@@ -151,7 +117,7 @@ def part_b(dev, rounds, periods, lines, streams=1):
             times[r]["pruned"].append(statistics.median(per["pruned"]))
     for r in worlds:
         t = times[r]
-        lines.append(f"{r:>6}  {cell(t['all']):>30}  {cell(t['acc']):>30}  {cell(t['pruned']):>30}  "
+        lines.append(f"{r:>6}  {cell(t['all'], 9, 3):>30}  {cell(t['acc'], 9, 3):>30}  {cell(t['pruned'], 9, 3):>30}  "
                      f"{statistics.mean(ncirc[r]['all']):>13.1f}  {statistics.mean(ncirc[r]['pruned']):>24.1f}")
         print(lines[-1], flush=True)
     t0, t5 = statistics.median(times[0.0]["all"]), statistics.median(times[0.5]["all"])
@@ -177,12 +143,7 @@ def main():
     part_a(dev, args.rounds, args.iters, lines)
     part_b(dev, args.rounds, args.periods, lines)
     part_b(dev, args.rounds, args.periods, lines, streams=9)
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    write_report(lines, args.out)
 
 
 if __name__ == "__main__":

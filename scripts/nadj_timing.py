@@ -3,10 +3,10 @@
 For every configuration (B, n, L, T) and noise point three variants compute the per-sample gradients G (B, P) and
 dw (P,), P = 2nL, on the same inputs:
   nadj      qd_qsim_noisy_adjoint (one adjoint pass for all trajectories that live on the noiseless state, one per
-            rebuilding trajectory), then qd_reduce_slab
+            rebuilding trajectory), then reduce_slab
   onchip    qd_qsim_noisy_pshift at 1024 shots (2P shifted circuits per sample, each with its own error
-            realisations), then qd_reduce_slab
-  adjoint   the noiseless adjoint (hip_qsim_bwd_slab) and qd_reduce_slab, for scale
+            realisations), then reduce_slab
+  adjoint   the noiseless adjoint (hip_qsim_bwd_slab) and reduce_slab, for scale
 Each variant is captured once as a HIP graph of ITERS back-to-back repetitions (so the host's launch rate is not what
 is timed), warmed up, and replayed between two events; the variants alternate within a round and the table gives the
 median and the min .. max over the rounds, per repetition.  The share of rebuilding trajectories is read from the
@@ -15,7 +15,6 @@ frames the kernel reports.
     python scripts/nadj_timing.py [--rounds 5] [--iters 10] [--out profiles/nadj_timing.txt]
 """
 import argparse
-import ctypes
 import math
 import os
 import statistics
@@ -25,20 +24,14 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from quantum_distributed_machine_learning_ris_channel_estimation_amd import _native as nat  # noqa: E402
 from quantum_distributed_machine_learning_ris_channel_estimation_amd.ops import quantum as Q  # noqa: E402
+from quantum_distributed_machine_learning_ris_channel_estimation_amd.utils.profiling import cell, time_graphed, write_report  # noqa: E402
 
 CONFIGS = [(2304, 8, 3, 64), (256, 12, 3, 16)]
 POINTS = [("zero", Q.NoiseModel()), ("1e-3/1e-2/.02", Q.NoiseModel(1e-3, 1e-2, 0.02, 0.02))]
 SHOTS = 1024
 SEED = 1234
 CTR = 5
-
-
-def reduce_slab(G, dw):
-    r = nat.fn(nat.hip_lib(), "qd_reduce_slab", [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                                 ctypes.c_float, ctypes.c_void_p])
-    nat.check(r(nat.ptr(G), nat.ptr(dw), G.shape[0], G.shape[1], 0.0, nat.stream_ptr(G.device)), "qd_reduce_slab")
 
 
 def variants(B, n, L, T, noise, dev):
@@ -57,14 +50,14 @@ def variants(B, n, L, T, noise, dev):
 
     def nadj(frames=None):
         Q.hip_qsim_noisy_adjoint(x, w, gE, G, noise, T, SEED, CTR, frames=frames)
-        reduce_slab(G, dw)
+        Q.reduce_slab(G, dw)
 
     def onchip():
         Q.hip_qsim_noisy_pshift(x, w, gE, G1, shots=SHOTS, seed=SEED, ctr0=CTR, noise=noise, trajectories=T)
-        reduce_slab(G1, dw1)
+        Q.reduce_slab(G1, dw1)
 
     def adjoint():
-        reduce_slab(Q.hip_qsim_bwd_slab(x, w, gE, dx), dw0)
+        Q.reduce_slab(Q.hip_qsim_bwd_slab(x, w, gE, dx), dw0)
 
     nadj(frames)
     onchip()
@@ -77,14 +70,6 @@ def variants(B, n, L, T, noise, dev):
     if noise.is_zero:
         assert float((G[:, 0:2 * n:2] - dx).abs().max()) <= 2e-4
     return {"nadj": nadj, "onchip": onchip, "adjoint": adjoint}, share, err
-
-
-def graph_of(fn, iters):
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(iters):
-            fn()
-    return g
 
 
 def main():
@@ -105,34 +90,16 @@ def main():
     for B, n, L, T in CONFIGS:
         for name, noise in POINTS:
             fns, share, err = variants(B, n, L, T, noise, dev)
-            graphs = {k: graph_of(f, args.iters) for k, f in fns.items()}
-            for g in graphs.values():   # warm-up
-                g.replay()
-                g.replay()
-            torch.cuda.synchronize()
-            times = {k: [] for k in graphs}
-            for _ in range(args.rounds):
-                for k, g in graphs.items():
-                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    a.record()
-                    g.replay()
-                    b.record()
-                    b.synchronize()
-                    times[k].append(a.elapsed_time(b) * 1e3 / args.iters)
-            cell = {k: f"{statistics.median(v):9.1f} ({min(v):.1f} .. {max(v):.1f})" for k, v in times.items()}
+            times = time_graphed(fns, args.iters, args.rounds)
+            cells = {k: cell(v, 9) for k, v in times.items()}
             ratio = statistics.median(times["onchip"]) / statistics.median(times["nadj"])
             over = statistics.median(times["nadj"]) / statistics.median(times["adjoint"])
             apart = "yes" if max(times["nadj"]) < min(times["onchip"]) else "NO"
-            lines.append(f"{B:>5} {n:>3} {L:>2} {T:>3} {name:>14}  {cell['nadj']:>28}  {cell['onchip']:>30}  "
-                         f"{cell['adjoint']:>24}  {ratio:>11.2f}  {apart:>12}  {over:>12.2f}  {share:>16.4f}  "
+            lines.append(f"{B:>5} {n:>3} {L:>2} {T:>3} {name:>14}  {cells['nadj']:>28}  {cells['onchip']:>30}  "
+                         f"{cells['adjoint']:>24}  {ratio:>11.2f}  {apart:>12}  {over:>12.2f}  {share:>16.4f}  "
                          f"{err:.2e}")
             print(lines[-1], flush=True)
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    write_report(lines, args.out)
 
 
 if __name__ == "__main__":

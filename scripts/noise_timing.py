@@ -25,6 +25,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from quantum_distributed_machine_learning_ris_channel_estimation_amd.ops import quantum as Q  # noqa: E402
+from quantum_distributed_machine_learning_ris_channel_estimation_amd.utils.profiling import cell, time_graphed, write_report  # noqa: E402
 
 CONFIGS = [(2304, 8, 3, 1024, 64), (2304, 12, 3, 1024, 16)]
 POINTS = {"zero": Q.NoiseModel(), "1e-3/1e-2/2%": Q.NoiseModel(p1=1e-3, p2=1e-2, readout01=0.02, readout10=0.02)}
@@ -80,14 +81,6 @@ def variants(B, n, L, shots, T, noise, dev):
     return {"noisy": noisy, "noisy-1wg": noisy_1wg, "noisy-8": noisy_split, "no-noise": no_noise, "every-traj": every_traj}, rebuilt
 
 
-def graph_of(fn, iters):
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(iters):
-            fn()
-    return g
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -103,34 +96,16 @@ def main():
     for B, n, L, shots, T in CONFIGS:
         for name, noise in POINTS.items():
             fns, rebuilt = variants(B, n, L, shots, T, noise, dev)
-            graphs = {k: graph_of(f, args.iters) for k, f in fns.items()}
-            for g in graphs.values():   # warm-up
-                g.replay()
-                g.replay()
-            torch.cuda.synchronize()
-            times = {k: [] for k in graphs}
-            for _ in range(args.rounds):
-                for k, g in graphs.items():
-                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    a.record()
-                    g.replay()
-                    b.record()
-                    b.synchronize()
-                    times[k].append(a.elapsed_time(b) * 1e3 / args.iters)
-            cell = {k: f"{statistics.median(v):8.1f} ({min(v):.1f} .. {max(v):.1f})" for k, v in times.items()}
+            times = time_graphed(fns, args.iters, args.rounds)
+            cells = {k: cell(v, 8) for k, v in times.items()}
             med = {k: statistics.median(v) for k, v in times.items()}
             apart = max(times["noisy"]) < min(times["every-traj"]) and max(times["noisy-1wg"]) < min(times["every-traj"])
-            lines.append(f"{B:>5} {n:>3} {L:>2} {shots:>6} {T:>4} {name:>13} {Q.noise_split(T, n):>5}  {cell['noisy']:>26}  "
-                         f"{cell['noisy-1wg']:>26}  {cell['noisy-8']:>26}  {cell['no-noise']:>26}  "
-                         f"{cell['every-traj']:>30}  {med['noisy'] / med['no-noise']:>14.2f}  "
+            lines.append(f"{B:>5} {n:>3} {L:>2} {shots:>6} {T:>4} {name:>13} {Q.noise_split(T, n):>5}  {cells['noisy']:>26}  "
+                         f"{cells['noisy-1wg']:>26}  {cells['noisy-8']:>26}  {cells['no-noise']:>26}  "
+                         f"{cells['every-traj']:>30}  {med['noisy'] / med['no-noise']:>14.2f}  "
                          f"{med['every-traj'] / med['noisy']:>16.2f}  {rebuilt:7.3f}"
                          f"{'' if apart else '   (ranges overlap)'}")
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    write_report(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -3,11 +3,11 @@
 For every configuration (B, n, L, shots, T) and noise point three variants compute the per-sample gradients G (B, P)
 and dw (P,), P = 2nL, on the same inputs:
   onchip    qd_qsim_noisy_pshift (the state that enters a layer built once per workgroup and kept; per circuit one
-            noiseless state for the error-free trajectories, the others rebuilt), then qd_reduce_slab
+            noiseless state for the error-free trajectories, the others rebuilt), then reduce_slab
   composed  what a user could do without it: 2P launches of qd_qsim_noisy_shots_fwd, one per shifted circuit with its
             shifted weights and its counter c + ((1 + 2p + s) << 48), then the contraction with gE and the sum over
             the batch in torch
-  pshift    the noiseless qd_qsim_pshift at the same shots and qd_reduce_slab, for scale
+  pshift    the noiseless qd_qsim_pshift at the same shots and reduce_slab, for scale
 Each variant is captured once as a HIP graph of ITERS back-to-back repetitions (so the host's launch rate is not what
 is timed), warmed up, and replayed between two events; the variants alternate within a round and the table gives the
 median and the min .. max over the rounds, per repetition.  First the kernel's expectations are compared with the
@@ -17,7 +17,6 @@ a CDF word differently.
     python scripts/onchip_timing.py [--rounds 5] [--iters 10] [--out profiles/onchip_timing.txt]
 """
 import argparse
-import ctypes
 import math
 import os
 import statistics
@@ -27,19 +26,13 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from quantum_distributed_machine_learning_ris_channel_estimation_amd import _native as nat  # noqa: E402
 from quantum_distributed_machine_learning_ris_channel_estimation_amd.ops import quantum as Q  # noqa: E402
+from quantum_distributed_machine_learning_ris_channel_estimation_amd.utils.profiling import cell, time_graphed, write_report  # noqa: E402
 
 CONFIGS = [(2304, 8, 3, 1024, 64), (256, 12, 3, 1024, 16)]
 POINTS = [("zero", Q.NoiseModel()), ("1e-3/1e-2/.02", Q.NoiseModel(1e-3, 1e-2, 0.02, 0.02))]
 SEED = 1234
 CTR = 5
-
-
-def reduce_slab(G, dw):
-    r = nat.fn(nat.hip_lib(), "qd_reduce_slab", [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                                 ctypes.c_float, ctypes.c_void_p])
-    nat.check(r(nat.ptr(G), nat.ptr(dw), G.shape[0], G.shape[1], 0.0, nat.stream_ptr(G.device)), "qd_reduce_slab")
 
 
 def variants(B, n, L, shots, T, noise, dev):
@@ -64,7 +57,7 @@ def variants(B, n, L, shots, T, noise, dev):
 
     def onchip(Epm=None):
         Q.hip_qsim_noisy_pshift(x, w, gE, G, Epm, shots=shots, seed=SEED, ctr0=CTR, noise=noise, trajectories=T)
-        reduce_slab(G, dw)
+        Q.reduce_slab(G, dw)
 
     def composed():
         for c in range(2 * P):
@@ -76,7 +69,7 @@ def variants(B, n, L, shots, T, noise, dev):
 
     def pshift():
         Q.hip_qsim_pshift(x, w, gE, G0, shots=shots, seed=SEED, ctr0=CTR)
-        reduce_slab(G0, dw0)
+        Q.reduce_slab(G0, dw0)
 
     onchip(Epm)
     composed()
@@ -86,14 +79,6 @@ def variants(B, n, L, shots, T, noise, dev):
     err = float(((G - out["G"]).abs() / gE.abs().sum(1, keepdim=True)).max())
     assert same >= 0.9 and err <= 0.05, f"the kernel and the composition disagree: {same:.4f} equal, max {err:.2e}"
     return {"onchip": onchip, "composed": composed, "pshift": pshift}, same, err
-
-
-def graph_of(fn, iters):
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(iters):
-            fn()
-    return g
 
 
 def main():
@@ -112,34 +97,16 @@ def main():
     for B, n, L, shots, T in CONFIGS:
         for name, noise in POINTS:
             fns, same, err = variants(B, n, L, shots, T, noise, dev)
-            graphs = {k: graph_of(f, args.iters) for k, f in fns.items()}
-            for g in graphs.values():   # warm-up
-                g.replay()
-                g.replay()
-            torch.cuda.synchronize()
-            times = {k: [] for k in graphs}
-            for _ in range(args.rounds):
-                for k, g in graphs.items():
-                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    a.record()
-                    g.replay()
-                    b.record()
-                    b.synchronize()
-                    times[k].append(a.elapsed_time(b) * 1e3 / args.iters)
-            cell = {k: f"{statistics.median(v):9.1f} ({min(v):.1f} .. {max(v):.1f})" for k, v in times.items()}
+            times = time_graphed(fns, args.iters, args.rounds)
+            cells = {k: cell(v, 9) for k, v in times.items()}
             ratio = statistics.median(times["composed"]) / statistics.median(times["onchip"])
             over = statistics.median(times["onchip"]) / statistics.median(times["pshift"])
             apart = "yes" if max(times["onchip"]) < min(times["composed"]) else "NO"
-            lines.append(f"{B:>5} {n:>3} {L:>2} {shots:>6} {T:>3} {name:>14}  {cell['onchip']:>30}  "
-                         f"{cell['composed']:>30}  {cell['pshift']:>28}  {ratio:>15.2f}  {apart:>12}  {over:>13.2f}  "
+            lines.append(f"{B:>5} {n:>3} {L:>2} {shots:>6} {T:>3} {name:>14}  {cells['onchip']:>30}  "
+                         f"{cells['composed']:>30}  {cells['pshift']:>28}  {ratio:>15.2f}  {apart:>12}  {over:>13.2f}  "
                          f"{same:>15.5f}  {err:.2e}")
             print(lines[-1], flush=True)
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    write_report(lines, args.out)
 
 
 if __name__ == "__main__":

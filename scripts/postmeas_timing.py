@@ -24,51 +24,14 @@ from quantum_distributed_machine_learning_ris_channel_estimation_amd.models.esti
 from quantum_distributed_machine_learning_ris_channel_estimation_amd.ops.optim import FlatParamSpace, make_optimizer  # noqa: E402
 from quantum_distributed_machine_learning_ris_channel_estimation_amd.ops.quantum import NoiseModel  # noqa: E402
 from quantum_distributed_machine_learning_ris_channel_estimation_amd.train.engine import ClassifierStep  # noqa: E402
+from quantum_distributed_machine_learning_ris_channel_estimation_amd.utils.profiling import (alternate, cell, graph_of,  # noqa: E402
+                                                                                             write_report)
 
 N, L, T, SHOTS, SEED = 8, 3, 64, 1024, 1234
 NOISE = NoiseModel(1e-3, 1e-2, 0.02, 0.02)
 _p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 POST = {"off": {}, "norm": dict(post_norm=True),
         "norm + 5 levels": dict(post_norm=True, post_quant_levels=5, post_quant_weight=0.1)}
-
-
-def graph_of(run, warm=3):
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        for _ in range(warm):
-            run()
-    torch.cuda.current_stream().wait_stream(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        run()
-    return g
-
-
-def timed(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def cell(v, scale=1.0):
-    return f"{statistics.median(v) * scale:9.3f} ({min(v) * scale:.3f} .. {max(v) * scale:.3f})"
-
-
-def alternate(fns, rounds, iters):
-    for f in fns.values():
-        f()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, f in fns.items():
-            times[k].append(timed(f, iters))
-    return times
 
 
 def heads(dev, B, n, C, launches):
@@ -143,33 +106,28 @@ def main():
         t = alternate(fns, args.rounds, args.iters)
         base = statistics.median(t["qd_qsc_head"])
         for k, v in t.items():
-            lines.append(f"  ({B}, {n}, {C})  {k:>24}  {cell(v, 1000.0 / launches):>30}  x{statistics.median(v) / base:5.2f}")
+            lines.append(f"  ({B}, {n}, {C})  {k:>24}  {cell(v, 9, 3, 1000.0 / launches):>30}  x{statistics.median(v) / base:5.2f}")
             print(lines[-1], flush=True)
             head_diff[(n, k)] = (statistics.median(v) - base) * 1000.0 / launches
         del fns, keep
     lines.append(f"(b) the fused measured step (noisy_adjoint, n = {N}, L = {L}, T = {T}, {SHOTS} shots, 9 x 256 samples), "
                  f"graphed; ms per step ({args.iters} replays per round and variant)")
-    graphs = {k: graph_of(step_world(dev, p)) for k, p in POST.items()}
+    graphs = {k: graph_of(step_world(dev, p), warm=3) for k, p in POST.items()}
     t = alternate({k: g.replay for k, g in graphs.items()}, args.rounds, args.iters)
     off = statistics.median(t["off"])
     spread = max(max(v) - min(v) for v in t.values()) * 1000.0
     for k, v in t.items():
         if k == "off":
-            lines.append(f"  {k:>16}  {cell(v):>30}  (widest round-to-round spread of the three variants {spread:.1f} us)")
+            lines.append(f"  {k:>16}  {cell(v, 9, 3):>30}  (widest round-to-round spread of the three variants {spread:.1f} us)")
         else:
             gap = (statistics.median(v) - off) * 1000.0
-            lines.append(f"  {k:>16}  {cell(v):>30}  on - off {gap:8.1f} us   (head alone, pm - plain: "
+            lines.append(f"  {k:>16}  {cell(v, 9, 3):>30}  on - off {gap:8.1f} us   (head alone, pm - plain: "
                          f"{head_diff[(N, 'head_pm ' + k)]:6.1f} us)")
         print(lines[-1], flush=True)
     lines.append("registers (hipcc -O3 -ffp-contract=fast, packed fp32 off; scripts/resource_usage.py): the step's (8, 3) head "
                  "sits at 128 VGPRs with no scratch -- no slack, a compiler update may tip it into scratch; every C <= 3 "
                  "head up to n = 13 has none; the C = 4 heads at n = 8, 12, 13 spill 36 / 44 / 72 B per lane, n >= 14 more")
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    write_report(lines, args.out)
 
 
 if __name__ == "__main__":

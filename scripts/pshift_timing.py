@@ -2,10 +2,10 @@
 
 For every configuration (B, n, L, shots) three variants compute the per-sample gradients G (B, P) and dw (P,),
 P = 2nL, on the same inputs:
-  pshift    qd_qsim_pshift (the state that enters a layer built once per workgroup and kept), then qd_reduce_slab
+  pshift    qd_qsim_pshift (the state that enters a layer built once per workgroup and kept), then reduce_slab
   composed  what a user could do without it: one qd_qsim_shots_fwd launch over 2P * B rows with 2P groups of shifted
             weights (every state rebuilt from scratch), then the contraction with gE and the sum over the batch in torch
-  adjoint   the exact adjoint backward (qsim.hip for n <= 10, qsim_big.hip above) and qd_reduce_slab, for scale
+  adjoint   the exact adjoint backward (qsim.hip for n <= 10, qsim_big.hip above) and reduce_slab, for scale
 Each variant is captured once as a HIP graph of ITERS back-to-back launches (so the host's launch rate is not what is
 timed), warmed up, and replayed between two events; the variants alternate within a round and the table gives the
 median and the min .. max over the rounds, per launch.  First the kernel's exact-mode G is compared with the
@@ -14,7 +14,6 @@ composition's (the exact forward on the same 2P groups of shifted weights).
     python scripts/pshift_timing.py [--rounds 5] [--iters 20] [--out profiles/pshift_timing.txt]
 """
 import argparse
-import ctypes
 import math
 import os
 import statistics
@@ -24,17 +23,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from quantum_distributed_machine_learning_ris_channel_estimation_amd import _native as nat  # noqa: E402
 from quantum_distributed_machine_learning_ris_channel_estimation_amd.ops import quantum as Q  # noqa: E402
+from quantum_distributed_machine_learning_ris_channel_estimation_amd.utils.profiling import cell, time_graphed, write_report  # noqa: E402
 
 CONFIGS = [(2304, 8, 3, 256), (2304, 8, 3, 1024), (256, 12, 3, 1024)]
 SEED = 1234
-
-
-def reduce_slab(G, dw):
-    r = nat.fn(nat.hip_lib(), "qd_reduce_slab", [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                                 ctypes.c_float, ctypes.c_void_p])
-    nat.check(r(nat.ptr(G), nat.ptr(dw), G.shape[0], G.shape[1], 0.0, nat.stream_ptr(G.device)), "qd_reduce_slab")
 
 
 def variants(B, n, L, shots, dev):
@@ -64,14 +57,14 @@ def variants(B, n, L, shots, dev):
 
     def pshift():
         Q.hip_qsim_pshift(x, w, gE, G, shots=shots, seed=SEED)
-        reduce_slab(G, dw)
+        Q.reduce_slab(G, dw)
 
     def composed():
         Q.hip_qsim_shots_fwd(xs, ws, Es, None, shots, SEED, wgroup=B)
         contract()
 
     def adjoint():
-        reduce_slab(Q.hip_qsim_bwd_slab(x, w, gE, dx), dwa)
+        Q.reduce_slab(Q.hip_qsim_bwd_slab(x, w, gE, dx), dwa)
 
     # exact mode first: the kernel against the composition on the exact forward
     Q.hip_qsim_pshift(x, w, gE, G, shots=0)
@@ -85,14 +78,6 @@ def variants(B, n, L, shots, dev):
     adjoint()
     torch.cuda.synchronize()
     return {"pshift": pshift, "composed": composed, "adjoint": adjoint}, err
-
-
-def graph_of(fn, iters):
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(iters):
-            fn()
-    return g
 
 
 def main():
@@ -109,31 +94,13 @@ def main():
              f"composed/pshift  ranges apart  max|G_exact-G_composed|/sum|gE|"]
     for B, n, L, shots in CONFIGS:
         fns, err = variants(B, n, L, shots, dev)
-        graphs = {k: graph_of(f, args.iters) for k, f in fns.items()}
-        for g in graphs.values():   # warm-up
-            g.replay()
-            g.replay()
-        torch.cuda.synchronize()
-        times = {k: [] for k in graphs}
-        for _ in range(args.rounds):
-            for k, g in graphs.items():
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                g.replay()
-                b.record()
-                b.synchronize()
-                times[k].append(a.elapsed_time(b) * 1e3 / args.iters)
-        cell = {k: f"{statistics.median(v):9.1f} ({min(v):.1f} .. {max(v):.1f})" for k, v in times.items()}
+        times = time_graphed(fns, args.iters, args.rounds)
+        cells = {k: cell(v, 9) for k, v in times.items()}
         ratio = statistics.median(times["composed"]) / statistics.median(times["pshift"])
         apart = "yes" if max(times["pshift"]) < min(times["composed"]) else "NO"
-        lines.append(f"{B:>5} {n:>3} {L:>2} {shots:>6}  {cell['pshift']:>28}  {cell['composed']:>28}  "
-                     f"{cell['adjoint']:>24}  {ratio:>15.2f}  {apart:>12}  {err:.2e}")
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+        lines.append(f"{B:>5} {n:>3} {L:>2} {shots:>6}  {cells['pshift']:>28}  {cells['composed']:>28}  "
+                     f"{cells['adjoint']:>24}  {ratio:>15.2f}  {apart:>12}  {err:.2e}")
+    write_report(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -20,6 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from quantum_distributed_machine_learning_ris_channel_estimation_amd.ops import quantum as Q  # noqa: E402
+from quantum_distributed_machine_learning_ris_channel_estimation_amd.utils.profiling import cell, time_graphed, write_report  # noqa: E402
 
 CONFIGS = [(2304, 8, 3, 256), (2304, 8, 3, 1024), (2304, 8, 3, 4096), (2304, 12, 3, 1024)]
 SEED = 1234
@@ -52,14 +53,6 @@ def variants(B, n, L, shots, dev):
     return {"fused": fused, "two-stage": two_stage, "exact": exact}, float((E - Ex).abs().max())
 
 
-def graph_of(fn, iters):
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(iters):
-            fn()
-    return g
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -74,30 +67,12 @@ def main():
              f"two-stage/fused  max|E_shots-E_exact|"]
     for B, n, L, shots in CONFIGS:
         fns, dE = variants(B, n, L, shots, dev)
-        graphs = {k: graph_of(f, args.iters) for k, f in fns.items()}
-        for g in graphs.values():   # warm-up
-            g.replay()
-            g.replay()
-        torch.cuda.synchronize()
-        times = {k: [] for k in graphs}
-        for _ in range(args.rounds):
-            for k, g in graphs.items():
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                g.replay()
-                b.record()
-                b.synchronize()
-                times[k].append(a.elapsed_time(b) * 1e3 / args.iters)
-        cell = {k: f"{statistics.median(v):8.1f} ({min(v):.1f} .. {max(v):.1f})" for k, v in times.items()}
+        times = time_graphed(fns, args.iters, args.rounds)
+        cells = {k: cell(v, 8) for k, v in times.items()}
         ratio = statistics.median(times["two-stage"]) / statistics.median(times["fused"])
-        lines.append(f"{B:>5} {n:>3} {L:>2} {shots:>6}  {cell['fused']:>24}  {cell['two-stage']:>24}  "
-                     f"{cell['exact']:>24}  {ratio:>15.2f}  {dE:.4f}")
-    text = "\n".join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+        lines.append(f"{B:>5} {n:>3} {L:>2} {shots:>6}  {cells['fused']:>24}  {cells['two-stage']:>24}  "
+                     f"{cells['exact']:>24}  {ratio:>15.2f}  {dE:.4f}")
+    write_report(lines, args.out)
 
 
 if __name__ == "__main__":

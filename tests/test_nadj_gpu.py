@@ -65,11 +65,7 @@ def launch(x, w, gE, noise, T, seed=SEED, ctr0=CTR, cptr=None, want=True):
 
 
 def reduce_slab(G):
-    B, P = G.shape
-    dw = torch.empty(P, device=G.device)
-    r = nat.fn(nat.hip_lib(), "qd_reduce_slab", [Q._p, Q._p, Q._i, Q._i, Q._f, Q._p])
-    nat.check(r(nat.ptr(G), nat.ptr(dw), B, P, 0.0, nat.stream_ptr(G.device)), "qd_reduce_slab")
-    return dw
+    return Q.reduce_slab(G, torch.empty(G.shape[1], device=G.device))
 
 
 @pytest.mark.parametrize("rates", ["hi", "lo"])

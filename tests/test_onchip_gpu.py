@@ -228,9 +228,7 @@ def test_autograd(cuda, n, L, B, G, T, shots):
     assert torch.equal(E, qsim(x, w, "hip", shots=shots, seed=SEED_HI, counter=CTR_HI, noise=noise, trajectories=T))
     (E * gE).sum().backward()
     assert torch.equal(xa.grad, Gd[:, 0:2 * n:2])
-    dw = torch.empty(P, device=cuda)
-    r = nat.fn(nat.hip_lib(), "qd_reduce_slab", [Q._p, Q._p, Q._i, Q._i, Q._f, Q._p])
-    nat.check(r(nat.ptr(Gd), nat.ptr(dw), B, P, 0.0, nat.stream_ptr(x.device)), "qd_reduce_slab")
+    dw = Q.reduce_slab(Gd, torch.empty(P, device=cuda))
     got = wa.grad if G == 0 else wa.grad[0]
     assert torch.equal(got.reshape(-1), dw)
     err = (dw.double() - Gd.double().sum(0)).abs()
