@@ -183,9 +183,10 @@ QD_API void qd_cpu_philox4x32(const uint32_t* ctr4, const uint32_t* key2, uint32
 
 // Finite-shot <Z_i> from fp32 probabilities, sequentially: the sampling contract of csrc/hip/qsim_shots.hip (see its
 // header), bit for bit.  probs (B, 2^n) fp32, a normalised distribution; E (B, n) fp32; counts (B, n) int32, nullable.
-QD_API int qd_cpu_sample_z(const float* probs, float* E, int32_t* counts, int B, int n, int shots, uint64_t seed,
-                           uint64_t ctr) {
-  if (n < 2 || n > 12 || shots < 1 || shots > (1 << 20)) return 1;
+namespace {
+int sample_z_rows(const float* probs, float* E, int32_t* counts, int B, int n, int shots, uint64_t seed, uint64_t ctr,
+                  int nmax) {
+  if (n < 2 || n > nmax || shots < 1 || shots > (1 << 20)) return 1;
   const size_t D = size_t(1) << n;
   const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
 #pragma omp parallel for schedule(static)
@@ -217,6 +218,18 @@ QD_API int qd_cpu_sample_z(const float* probs, float* E, int32_t* counts, int B,
     }
   }
   return 0;
+}
+}  // namespace
+
+QD_API int qd_cpu_sample_z(const float* probs, float* E, int32_t* counts, int B, int n, int shots, uint64_t seed,
+                           uint64_t ctr) {
+  return sample_z_rows(probs, E, counts, B, n, shots, seed, ctr, 12);   // (the range of csrc/hip/qsim_shots.hip)
+}
+
+// The same contract for 2 <= n <= 16: the oracle of the streamed sampler (csrc/hip/qsim_stream_shots.hip) above 12.
+QD_API int qd_cpu_sample_z_wide(const float* probs, float* E, int32_t* counts, int B, int n, int shots, uint64_t seed,
+                                uint64_t ctr) {
+  return sample_z_rows(probs, E, counts, B, n, shots, seed, ctr, 16);
 }
 
 // ------------------------------------------------------------------------------- Pauli noise (csrc/hip/qsim_noise.hip)

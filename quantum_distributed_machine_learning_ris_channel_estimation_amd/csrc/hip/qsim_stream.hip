@@ -36,6 +36,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "qsim_shots_dev.h"   // prob_of, quantise: the finite-shot contract's fp32 probability and its 2^30 word
 
 #ifndef QD_STREAM_SWEEP
 #define QD_STREAM_SWEEP 0   // (1: pass A's adjoint sweeps psi and lambda together, as before round 6 -- A/B builds)
@@ -802,6 +803,69 @@ __global__ void __launch_bounds__(NT, 2) pass_b_fwd(const float* __restrict__ x,
     float o[N];
     block_sum_vec<N>(part, red, o);
     if (threadIdx.x < N) epart[((size_t)s * C::NTILE + t) * N + threadIdx.x] = o[threadIdx.x];
+  }
+}
+
+// The probabilities pass (finite shots at n = 13..16, csrc/hip/qsim_stream_shots.hip): the forward's last pass B with
+// the ring scatter of the non-last pass and |amplitude|^2 (qshots::prob_of: explicit roundings) stored instead of a
+// state -- probs[s * D + j] fp32 in natural order, the tile's two coalesced runs of 2048 with 16-byte stores.  RY on
+// qubits 8..11 only: the layer's RZ phases leave |a|^2 alone (as pass_b_fwd's LAST branch).  RT: runtot[s, j >> 11] =
+// the uint32 sum of qshots::quantise(p) over each of the two runs; the ring maps the sample's tiles one-to-one onto
+// its 2^(N-11) runs, so every run total is written once, by one workgroup.
+template <int N, bool RT>
+__global__ void __launch_bounds__(NT, 2) pass_b_probs(const float* __restrict__ x, const float* __restrict__ w, int L,
+                                                   int l, int wgroup, const cf* __restrict__ in,
+                                                   float* __restrict__ probs, uint32_t* __restrict__ runtot) {
+  using C = SG<N>;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float4* trig = reinterpret_cast<float4*>(smem);
+  uint32_t* red = reinterpret_cast<uint32_t*>(smem + 256);    // NWV * 2 words
+  cf* tp = reinterpret_cast<cf*>(smem + 512);
+  const int t = blockIdx.x, s = blockIdx.y, c = threadIdx.x;
+  const cf* src = in + (size_t)s * C::D + ((size_t)t << 12);
+  cf a[16];
+#pragma unroll
+  for (int h = 0; h < 16; ++h) a[h] = src[(h << 8) | c];
+  load_trig<N>(trig, x, w, s, L, l, wgroup);
+  __syncthreads();
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const float4 tg = trig[8 + b];
+#pragma unroll
+    for (int h = 0; h < 16; ++h)
+      if (!((h >> b) & 1)) gate_ry(a[h], a[h | (1 << b)], tg);
+  }
+#pragma unroll
+  for (int h = 0; h < 16; ++h) tp[ring_fwd<N>((t << 12) | (h << 8) | c) & 4095] = a[h];
+  __syncthreads();
+  const int A0 = ring_fwd<N>(t << 12) >> 12, A1 = ring_fwd<N>((t << 12) | 2048) >> 12;
+  float* dst = probs + (size_t)s * C::D;
+  uint32_t rt[2] = {0u, 0u};
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {   // u = 0, 1: the run below bit 11 of the image; 2, 3: the run above
+    const int i = 4 * c + 4 * NT * u;
+    const float4 v0 = *lds16(tp + i), v1 = *lds16(tp + i + 2);
+    const float4 p = make_float4(qshots::prob_of(qshots::cf{v0.x, v0.y}), qshots::prob_of(qshots::cf{v0.z, v0.w}),
+                                 qshots::prob_of(qshots::cf{v1.x, v1.y}), qshots::prob_of(qshots::cf{v1.z, v1.w}));
+    *reinterpret_cast<float4*>(dst + (i | ((u >> 1 ? A1 : A0) << 12))) = p;
+    if constexpr (RT)
+      rt[u >> 1] += qshots::quantise(p.x) + qshots::quantise(p.y) + qshots::quantise(p.z) + qshots::quantise(p.w);
+  }
+  if constexpr (RT) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) rt[r] += __shfl_xor(rt[r], m);
+      if (lane == 0) red[wv * 2 + r] = rt[r];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+      uint32_t o = 0;
+#pragma unroll
+      for (int k = 0; k < NWV; ++k) o += red[k * 2 + threadIdx.x];
+      runtot[(size_t)s * (2 * C::NTILE) + 2 * (threadIdx.x ? A1 : A0) + threadIdx.x] = o;
+    }
   }
 }
 
@@ -1589,6 +1653,51 @@ static int fwd(const float* x, const float* w, float* E, int B, int L, int wgrou
   }
   if (E) hipLaunchKernelGGL(reduce_e<N>, dim3((B * N + 255) / 256), dim3(256), 0, st, epart, E, B);
   return (int)hipGetLastError();
+}
+
+// The forward's passes (as fwd, no state kept) with the probabilities pass in place of the last pass B: probs (B, D)
+// fp32, runtot (nullable) (B, D / 2048) uint32.  ws: the forward's workspace.
+template <int N>
+static int probs_fwd(const float* x, const float* w, float* probs, uint32_t* runtot, int B, int L, int wgroup,
+                     char* ws, hipStream_t st) {
+  using C = SG<N>;
+  using S = Smem<N>;
+  const size_t sb = state_bytes(N, B);
+  cf* T = reinterpret_cast<cf*>(ws);
+  cf* S0 = reinterpret_cast<cf*>(ws + sb + epart_bytes(N, B));
+  static bool attr = false;
+  if (!attr) {
+    (void)allow_lds(pass_a_fwd<N, true>, S::A_FWD_GEN);
+    (void)allow_lds(pass_a_fwd<N, false>, S::A_FWD);
+    (void)allow_lds(pass_b_fwd<N, false>, S::B_FWD);
+    attr = true;
+  }
+  const dim3 ga(ROWS, B), gb(C::NTILE, B);
+  for (int l = 1; l < L; ++l) {
+    if (l == 1)
+      hipLaunchKernelGGL((pass_a_fwd<N, true>), ga, dim3(NT), S::A_FWD_GEN, st, x, w, L, l, wgroup, nullptr, S0);
+    else
+      hipLaunchKernelGGL((pass_a_fwd<N, false>), ga, dim3(NT), S::A_FWD, st, x, w, L, l, wgroup, T, S0);
+    if (l < L - 1)
+      hipLaunchKernelGGL((pass_b_fwd<N, false>), gb, dim3(NT), S::B_FWD, st, x, w, L, l, wgroup, S0, T, nullptr);
+    else if (runtot != nullptr)
+      hipLaunchKernelGGL((pass_b_probs<N, true>), gb, dim3(NT), S::B_FWD, st, x, w, L, l, wgroup, S0, probs, runtot);
+    else
+      hipLaunchKernelGGL((pass_b_probs<N, false>), gb, dim3(NT), S::B_FWD, st, x, w, L, l, wgroup, S0, probs, runtot);
+  }
+  return (int)hipGetLastError();
+}
+
+// (csrc/hip/qsim_stream_shots.hip's entry points check the arguments)
+int probs_passes(const float* x, const float* w, float* probs, uint32_t* runtot, int B, int n, int L, int wgroup,
+                 char* ws, hipStream_t st) {
+  switch (n) {
+    case 13: return probs_fwd<13>(x, w, probs, runtot, B, L, wgroup, ws, st);
+    case 14: return probs_fwd<14>(x, w, probs, runtot, B, L, wgroup, ws, st);
+    case 15: return probs_fwd<15>(x, w, probs, runtot, B, L, wgroup, ws, st);
+    case 16: return probs_fwd<16>(x, w, probs, runtot, B, L, wgroup, ws, st);
+    default: return (int)hipErrorInvalidValue;
+  }
 }
 
 // Backward.  ws: [lambda 1][lambda 2][forward ws: T, <Z> partials][L - 1 kept states when psave is null].

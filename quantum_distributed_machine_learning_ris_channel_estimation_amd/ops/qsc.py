@@ -27,8 +27,8 @@ from .. import _native as nat
 from .slabsum import SlabBatch
 from ..ops.optim import FlatParamSpace
 from ..knobs import KNOBS
-from ..ops.quantum import (HIP_REG_MAX_QUBITS, HIP_SHOTS_MAX_QUBITS, counter_add, hip_measured_fwd, hip_measured_rows,
-                           hip_qsim_bwd_slab, resolve_measure, split_counter, stream_sim_ok)
+from ..ops.quantum import (HIP_REG_MAX_QUBITS, HIP_SHOTS_MAX_QUBITS, _hip_shots_limit, counter_add, hip_measured_fwd,
+                           hip_measured_rows, hip_qsim_bwd_slab, resolve_measure, split_counter, stream_sim_ok)
 
 _p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 
@@ -233,6 +233,8 @@ class QSCStepHIP:
             raise ValueError(f"a measured step supports 2 n L <= 256 (the fused backward's slab width), got n={n} L={L}")
         self.mode = mode = resolve_measure(diff_method, shots, noise, trajectories, shift_mask, n, L, "hip", dev,
                                            mask_shape=False)
+        if self.measured:   # (the measured step's kernels; the resolver admits plain shots up to 16 qubits)
+            _hip_shots_limit(n)
         self.diff_method, self.noise, self.trajectories, self.shots = diff_method, noise, mode.trajectories, mode.shots
         self.shot_seed = int(shot_seed)
         self.shift_mask = shift_mask
@@ -343,7 +345,8 @@ class QSCStepHIP:
         """Inference on the HIP kernels (x.shape[0] == B): preprocess CNN, the circuit with the clean
         master weights (no QuantumNAT noise), then a thread-per-sample head -> log-probabilities (B, C)
         and / or the argmax (B,) int64.  ``shots`` > 0: the circuit's <Z_i> are finite-shot estimates
-        (csrc/hip/qsim_shots.hip's fused kernel on the angles, n <= 12; ``seed`` / ``counter`` as in
+        (csrc/hip/qsim_shots.hip's fused kernel on the angles at n <= 12, the streamed simulator's finite-shot
+        forward, csrc/hip/qsim_stream_shots.hip, at n = 13..16; ``seed`` / ``counter`` as in
         ops.quantum.qsim).  ``noise`` / ``trajectories`` (with ``shots``): the shots are measured under that
         ``NoiseModel`` (csrc/hip/qsim_noise.hip).  ``valid`` (a model with ``postmeas``; default B): the real rows
         of a padded batch -- the batch statistics of the post-measurement normalization go over those only

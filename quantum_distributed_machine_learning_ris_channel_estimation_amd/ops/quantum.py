@@ -18,8 +18,10 @@ Here three interchangeable backends implement the SAME function:
                oracle.  Never selected implicitly on a GPU.
 
 Finite shots (``qsim(..., shots=N)``, ``qsim_probs``, ``sample_z``, ``counter_add``): <Z_i> estimated from N
-measurement shots of the final state -- csrc/hip/qsim_shots.hip (n <= 12) on ``hip``, simulate-then-sample on
-``cpu`` with the same integer sampling contract; by default gradients stay the exact adjoint (straight-through).
+measurement shots of the final state -- csrc/hip/qsim_shots.hip (n <= 12) and csrc/hip/qsim_stream_shots.hip (n =
+13..16 with L >= 2: probabilities, sampler and the fused forward, the exact adjoint behind it) on ``hip``,
+simulate-then-sample on ``cpu`` with the same integer sampling contract (``sample_z``: n <= 16 on both); by default
+gradients stay the exact adjoint (straight-through).
 
 Parameter shift (``qsim(..., diff_method="parameter_shift")``, ``pshift_rows``): the backward an on-chip QNN can
 measure -- two more runs of the circuit per parameter, one angle shifted by +-pi/2, exact or with the forward's
@@ -297,6 +299,7 @@ def _check_shapes(x: torch.Tensor, w: torch.Tensor) -> None:
 
 # ----------------------------------------------------------------------------- finite shots
 HIP_SHOTS_MAX_QUBITS = 12   # csrc/hip/qsim_shots.hip: state, ring gather buffer and CDF in one workgroup's LDS
+HIP_SAMPLER_MAX_QUBITS = 16  # sample_z, and with L >= 2 probabilities / plain shots: csrc/hip/qsim_stream_shots.hip
 MAX_SHOTS = 1 << 20
 _u64 = ctypes.c_uint64
 _M64 = (1 << 64) - 1
@@ -329,9 +332,23 @@ def counter_add(counter: torch.Tensor, delta: int = 1) -> None:
     nat.check(f(nat.ptr(counter), int(delta) & _M64, nat.stream_ptr(counter.device)), "qd_counter_add")
 
 
+def _stream_shots_ws(name: str, dims, device) -> Optional[torch.Tensor]:
+    """The workspace of a streamed finite-shot entry point (csrc/hip/qsim_stream_shots.hip), sized by its
+    ``<name>_workspace(*dims)``; None outside the entry point's range (it then refuses the call)."""
+    nbytes = nat.fn(nat.hip_lib(), name + "_workspace", [_i] * len(dims), ctypes.c_longlong)(*dims)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
 def hip_qsim_probs(x: torch.Tensor, w: torch.Tensor, probs: torch.Tensor, wgroup: int = 0) -> None:
-    """Raw launcher: probs (B, 2^n) fp32 = |amp_k|^2 in natural basis order; n <= 12."""
+    """Raw launcher: probs (B, 2^n) fp32 = |amp_k|^2 in natural basis order; n <= 12 (csrc/hip/qsim_shots.hip), or
+    n = 13..16 with L >= 2 on the streamed simulator (csrc/hip/qsim_stream.hip's probabilities pass)."""
     B, n = x.shape
+    if n > HIP_SHOTS_MAX_QUBITS:
+        name, L = "qd_qsim_stream_probs", w.shape[-3]
+        ws = _stream_shots_ws(name, (n, B, L), x.device)
+        f = nat.fn(nat.hip_lib(), name, [_p, _p, _p, _i, _i, _i, _i, _p, _p])
+        nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(probs), B, n, L, wgroup, _opt(ws), nat.stream_ptr(x.device)), name)
+        return
     f = nat.fn(nat.hip_lib(), "qd_qsim_probs", [_p, _p, _p, _i, _i, _i, _i, _p])
     nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(probs), B, n, w.shape[-3], wgroup, nat.stream_ptr(x.device)),
               "qd_qsim_probs")
@@ -339,7 +356,15 @@ def hip_qsim_probs(x: torch.Tensor, w: torch.Tensor, probs: torch.Tensor, wgroup
 
 def hip_sample_z(probs: torch.Tensor, E: torch.Tensor, counts: Optional[torch.Tensor], n: int, shots: int,
                  seed: int = 0, ctr0: int = 0, counter_ptr=None) -> None:
-    """Raw launcher: E (B, n) fp32 / counts (B, n) int32 (nullable) from `shots` draws of every row of probs."""
+    """Raw launcher: E (B, n) fp32 / counts (B, n) int32 (nullable) from `shots` draws of every row of probs; above
+    12 qubits (to 16) the block sampler of csrc/hip/qsim_stream_shots.hip."""
+    if n > HIP_SHOTS_MAX_QUBITS:
+        name, B = "qd_stream_sample_z", probs.shape[0]
+        ws = _stream_shots_ws(name, (n, B), probs.device)
+        f = nat.fn(nat.hip_lib(), name, [_p, _p, _p, _i, _i, _i, _u64, _u64, _p, _p, _p])
+        nat.check(f(nat.ptr(probs), nat.ptr(E), _opt(counts), B, n, shots, seed & _M64, ctr0 & _M64, counter_ptr,
+                    _opt(ws), nat.stream_ptr(probs.device)), name)
+        return
     f = nat.fn(nat.hip_lib(), "qd_sample_z", [_p, _p, _p, _i, _i, _i, _u64, _u64, _p, _p])
     nat.check(f(nat.ptr(probs), nat.ptr(E), _opt(counts), probs.shape[0], n, shots, seed & _M64, ctr0 & _M64,
                 counter_ptr, nat.stream_ptr(probs.device)), "qd_sample_z")
@@ -347,8 +372,17 @@ def hip_sample_z(probs: torch.Tensor, E: torch.Tensor, counts: Optional[torch.Te
 
 def hip_qsim_shots_fwd(x: torch.Tensor, w: torch.Tensor, E: torch.Tensor, counts: Optional[torch.Tensor], shots: int,
                        seed: int = 0, ctr0: int = 0, counter_ptr=None, wgroup: int = 0) -> None:
-    """Raw launcher of the fused kernel: state -> probabilities -> shots in one launch; n <= 12."""
+    """Raw launcher of the fused finite-shot forward: state -> probabilities -> shots in one launch (n <= 12), or
+    the streamed forward's passes, its probabilities pass and the block sampler (n = 13..16, L >= 2); only E / counts
+    leave the kernels' workspace."""
     B, n = x.shape
+    if n > HIP_SHOTS_MAX_QUBITS:
+        name, L = "qd_qsim_stream_shots_fwd", w.shape[-3]
+        ws = _stream_shots_ws(name.replace("_fwd", ""), (n, B, L), x.device)
+        f = nat.fn(nat.hip_lib(), name, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _u64, _u64, _p, _p, _p])
+        nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(E), _opt(counts), B, n, L, wgroup, shots, seed & _M64,
+                    ctr0 & _M64, counter_ptr, _opt(ws), nat.stream_ptr(x.device)), name)
+        return
     f = nat.fn(nat.hip_lib(), "qd_qsim_shots_fwd", [_p, _p, _p, _p, _i, _i, _i, _i, _i, _u64, _u64, _p, _p])
     nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(E), _opt(counts), B, n, w.shape[-3], wgroup, shots, seed & _M64,
                 ctr0 & _M64, counter_ptr, nat.stream_ptr(x.device)), "qd_qsim_shots_fwd")
@@ -359,11 +393,19 @@ def _hip_shots_limit(n: int) -> None:
         raise NotImplementedError(f"the HIP finite-shot kernels support n <= {HIP_SHOTS_MAX_QUBITS} qubits, got {n}")
 
 
+def _hip_stream_shots_limit(n: int, L: int) -> None:
+    """The range of the plain finite-shot kernels (probabilities, sampler, fused forward): n <= 12, and n = 13..16
+    with L >= 2 on the streamed simulator; every other measured kernel stops at ``_hip_shots_limit``."""
+    if not (n > HIP_SHOTS_MAX_QUBITS and stream_sim_ok(n, L)):
+        _hip_shots_limit(n)
+
+
 @torch.no_grad()
 def qsim_probs(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None,
                frames: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Outcome probabilities |amp_k|^2 of the QSC circuit, (B, 2^n) in natural basis order (the ``qml.probs``
-    counterpart): fp32 on ``hip`` (n <= 12), fp64 on ``cpu``, the eager simulator's on ``torch``.  No autograd.
+    counterpart): fp32 on ``hip`` (n <= 12, or n = 13..16 with L >= 2), fp64 on ``cpu``, the eager simulator's on
+    ``torch``.  No autograd.
 
     ``frames`` ((B, L, 2) int32, ``cpu`` only: the oracle of csrc/hip/qsim_noise.hip): row b's Pauli frames
     (a, b), applied behind the rings of layers 0 .. L-2; the last layer's frame acts on the outcome and is
@@ -375,7 +417,7 @@ def qsim_probs(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None,
         return _qsim_probs_framed(x, w, be, frames)
     _check_backend(be, x.device)
     if be == "hip":
-        _hip_shots_limit(n)
+        _hip_stream_shots_limit(n, w.shape[-3])
         x = x.detach().float().contiguous()
         w = w.detach().float().contiguous()
         probs = torch.empty(B, 1 << n, device=x.device, dtype=torch.float32)
@@ -399,15 +441,15 @@ def sample_z(probs: torch.Tensor, shots: int, seed: int = 0, counter=0, return_c
     """Finite-shot <Z_i> from outcome probabilities (B, 2^n), a normalised distribution per row (cast to fp32):
     E (B, n) fp32, and with ``return_counts`` also counts (B, n) int32, the shots that read 1 on wire i.
 
-    Dispatches on the tensor's device: csrc/hip/qsim_shots.hip on the GPU, the sequential C++ sampler on the
-    host -- the same integer contract (Philox4x32-10 keyed by ``seed``, counter (shot / 4, row, counter)), so the
-    two agree bit for bit on the same fp32 probabilities.  2 <= n <= 12."""
+    Dispatches on the tensor's device: csrc/hip/qsim_shots.hip (above 12 qubits csrc/hip/qsim_stream_shots.hip) on
+    the GPU, the sequential C++ sampler on the host -- the same integer contract (Philox4x32-10 keyed by ``seed``,
+    counter (shot / 4, row, counter)), so the two agree bit for bit on the same fp32 probabilities.  2 <= n <= 16."""
     shots = _check_shots(shots)
     if probs.dim() != 2 or probs.shape[1] < 4 or probs.shape[1] & (probs.shape[1] - 1):
         raise ValueError(f"probs must be (B, 2^n) with n >= 2, got {tuple(probs.shape)}")
     B, n = probs.shape[0], probs.shape[1].bit_length() - 1
-    if n > HIP_SHOTS_MAX_QUBITS:   # (the host sampler keeps the kernels' range: one contract)
-        raise NotImplementedError(f"the shot samplers support n <= {HIP_SHOTS_MAX_QUBITS} qubits, got {n}")
+    if n > HIP_SAMPLER_MAX_QUBITS:   # (the host sampler keeps the kernels' range: one contract)
+        raise NotImplementedError(f"the shot samplers support n <= {HIP_SAMPLER_MAX_QUBITS} qubits, got {n}")
     probs = probs.detach().float().contiguous()
     ctr0, cptr = split_counter(counter, probs.device)
     E = torch.empty(B, n, device=probs.device, dtype=torch.float32)
@@ -415,9 +457,9 @@ def sample_z(probs: torch.Tensor, shots: int, seed: int = 0, counter=0, return_c
     if B > 0 and probs.device.type == "cuda":
         hip_sample_z(probs, E, counts, n, shots, int(seed), ctr0, cptr)
     elif B > 0:
-        f = nat.fn(nat.cpu_lib(), "qd_cpu_sample_z", [_p, _p, _p, _i, _i, _i, _u64, _u64])
-        nat.check(f(nat.ptr(probs), nat.ptr(E), nat.ptr(counts), B, n, shots, int(seed) & _M64, ctr0),
-                  "qd_cpu_sample_z")
+        name = "qd_cpu_sample_z" if n <= HIP_SHOTS_MAX_QUBITS else "qd_cpu_sample_z_wide"   # (one body, two ranges)
+        f = nat.fn(nat.cpu_lib(), name, [_p, _p, _p, _i, _i, _i, _u64, _u64])
+        nat.check(f(nat.ptr(probs), nat.ptr(E), nat.ptr(counts), B, n, shots, int(seed) & _M64, ctr0), name)
     return (E, counts) if return_counts else E
 
 
@@ -712,7 +754,9 @@ def resolve_measure(diff_method, shots, noise, trajectories, shift_mask, n: int,
             raise ValueError("the torch backend has no noise model; use hip or cpu" if noise is not None else
                              "the torch backend has no finite-shot sampler; use hip or cpu")
         _check_backend(be, device)
-        if be == "hip":
+        if be == "hip" and noise is None:   # plain shots: also the streamed simulator's sizes
+            _hip_stream_shots_limit(n, L)
+        elif be == "hip":
             _hip_shots_limit(n)
         if noise is not None:
             _check_noise_shape(n, L)
@@ -722,7 +766,8 @@ def resolve_measure(diff_method, shots, noise, trajectories, shift_mask, n: int,
 def hip_measured_fwd(x: torch.Tensor, w: torch.Tensor, E: torch.Tensor, mode: MeasureMode, seed: int = 0,
                      ctr0: int = 0, counter_ptr=None, wgroup: int = 0) -> None:
     """The measured forward of a mode with shots, E (B, n) fp32: the noisy kernel under ``mode.noise``, else the
-    fused finite-shot one.  ``qsim`` and the fused step (ops/qsc.py) both launch through here."""
+    fused finite-shot one (above 12 qubits the streamed simulator's: ``hip_qsim_shots_fwd`` picks it).  ``qsim`` and
+    the fused step (ops/qsc.py) both launch through here."""
     if mode.noise is not None:
         hip_qsim_noisy_shots_fwd(x, w, E, None, mode.noise, mode.shots, mode.trajectories, seed, ctr0, counter_ptr,
                                  wgroup)
@@ -1060,7 +1105,9 @@ def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots:
     w[b // (B/G)] (independent QuantumNAT noise per data stream).
 
     ``shots`` (None / 0: the exact expectation): every <Z_i> is estimated from that many measurement shots of
-    the final state -- the fused kernel of csrc/hip/qsim_shots.hip on ``hip`` (n <= 12), simulate-then-sample
+    the final state -- the fused kernel of csrc/hip/qsim_shots.hip on ``hip`` (n <= 12; n = 13..16 with L >= 2 on
+    the streamed simulator, csrc/hip/qsim_stream_shots.hip, without noise and with the adjoint gradient only),
+    simulate-then-sample
     on ``cpu``; ``torch`` has no sampler.  The shots of a call are a function of (``seed``, ``counter``, row);
     ``counter`` is an int, or on ``hip`` a CUDA int64 / uint64 scalar tensor the kernel reads (advance it with
     ``counter_add`` after the call: graph replays then draw fresh shots).  The BACKWARD is the exact adjoint of
