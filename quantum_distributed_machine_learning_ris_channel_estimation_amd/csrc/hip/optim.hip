@@ -265,7 +265,7 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, float*
         m[i] = mi;
         v[i] = vi;
         p[i] = pj;
-        g[i] = gj;
+        if (a.prune_thr > 0.f || a.grad_scale != 1.f) g[i] = gj;   // (as the vector path: else the gradient is left alone)
         if (sh.out != nullptr && i >= sh.lo && i < sh.hi) {
           sh.out[i - sh.lo] = f32_to_bf16(p[i]);
           if (sh.out8 != nullptr) {
@@ -290,15 +290,27 @@ __global__ void __launch_bounds__(256) sgd_kernel(float* __restrict__ p, float* 
                                                   float* __restrict__ buf, long n, const float* __restrict__ lr_ptr,
                                                   const float* step_ptr, const float* __restrict__ skip,
                                                   float momentum, float weight_decay, float grad_scale,
+                                                  float prune_thr, unsigned int* __restrict__ pruned,
                                                   float* __restrict__ step_out, unsigned int* __restrict__ done) {
   if (skip != nullptr && *skip != 0.f) return;
   const float lr = *lr_ptr;
   const bool first = *step_ptr < 0.5f;
+  // pruning and the gradient write-back as adam_kernel: prune after the scale, the L2 term after pruning, the
+  // gradient stored as the update used it when either is on
+  const bool wb = prune_thr > 0.f || grad_scale != 1.f;
+  unsigned int cnt = 0;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    float gj = g[i] * grad_scale + weight_decay * p[i];
+    float gj = g[i] * grad_scale;
+    if (prune_thr > 0.f && !(fabsf(gj) > prune_thr)) { gj = 0.f; ++cnt; }
+    gj += weight_decay * p[i];
     float b = first ? gj : momentum * buf[i] + gj;
     buf[i] = b;
     p[i] -= lr * b;
+    if (wb) g[i] = gj;
+  }
+  if (pruned != nullptr && prune_thr > 0.f) {
+    float c = wave_sum((float)cnt);
+    if ((threadIdx.x & 63) == 0 && c > 0.f) atomicAdd(pruned, (unsigned int)c);
   }
   tick_if_last(step_out, done);
 }
@@ -440,6 +452,8 @@ QD_API int qd_adam_step_slabs(float* p, float* g, float* m, float* v, long n, co
   // streaming loads/stores for large ranges (profiles/r1_17_adam_nt.md)
   const bool nt = n - hole_n >= (1L << 20);
   const dim3 grid(grid_for(n - hole_n, max_grid > 0 ? max_grid : 2048) + sj.wg0[nj]);
+  // (every workgroup writes its |w| max partial to amax[blockIdx.x]: kAmaxParts slots)
+  if (shadow8 && grid.x > (unsigned)qd::kAmaxParts) return (int)hipErrorInvalidValue;
 #define QD_ADAM(NT_, SL_)                                                                                          \
   hipLaunchKernelGGL((adam_kernel<NT_, SL_>), grid, dim3(256), 0, st, p, g, m, v, n, lr, step, skip, pruned, a, step, \
                      done, sh, ps, hole_lo, hole_n, sj)
@@ -453,11 +467,12 @@ QD_API int qd_adam_step_slabs(float* p, float* g, float* m, float* v, long n, co
 }
 
 QD_API int qd_sgd_step(float* p, float* g, float* buf, long n, const float* lr, float* step, const float* skip,
-                       float momentum, float weight_decay, float grad_scale, unsigned int* done, void* stream) {
+                       float momentum, float weight_decay, float grad_scale, float prune_thr, unsigned int* pruned,
+                       unsigned int* done, void* stream) {
   if (n <= 0 || done == nullptr) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n * 4)), dim3(256), 0, st, p, g, buf, n, lr, step, skip, momentum,
-                     weight_decay, grad_scale, step, done);
+                     weight_decay, grad_scale, prune_thr, pruned, step, done);
   return (int)hipGetLastError();
 }
 

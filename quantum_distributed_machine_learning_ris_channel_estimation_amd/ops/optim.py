@@ -309,9 +309,10 @@ class FusedOptimizer:
         sp = lambda t: ctypes.c_void_p(t.data_ptr() + 4 * lo)
         step_p, done_p = nat.ptr(self.step_t[i:]), nat.ptr(self.done[i:])
         if self.kind == "sgd":
-            f = nat.fn(lib, "qd_sgd_step", [_p, _p, _p, _l, _p, _p, _p, _f, _f, _f, _p, _p])
+            f = nat.fn(lib, "qd_sgd_step", [_p, _p, _p, _l, _p, _p, _p, _f, _f, _f, _f, _p, _p, _p])
             nat.check(f(sp(s.flat), sp(s.grad), nat.ptr(self.buf[lo:]), hi - lo, nat.ptr(self.lr_t), step_p, skp,
-                        self.momentum, self.weight_decay, grad_scale, done_p, st), "sgd")
+                        self.momentum, self.weight_decay, grad_scale, self.prune_thr, nat.ptr(self.pruned), done_p,
+                        st), "sgd")
             if self.shadow is not None:
                 self.refresh_shadow()
             return
@@ -358,9 +359,14 @@ class FusedOptimizer:
             self.pruned += (~mask).sum().to(torch.int32)
             g.mul_(mask)
         lr = float(self.lr_t.item())
+        # d: the gradient the update uses -- with the L2 term unless the decay is decoupled.  Like the kernels, a step
+        # that scales or prunes stores d back as the gradient; any other step leaves the gradient alone
+        d = g
+        if self.weight_decay and self.kind != "adamw":
+            d = g.add_(p, alpha=self.weight_decay) if (grad_scale != 1.0 or self.prune_thr > 0) \
+                else g + self.weight_decay * p
         if self.kind == "sgd":
             buf = self.buf[lo:hi]
-            d = g + self.weight_decay * p if self.weight_decay else g
             if self.step_t[i].item() == 0:
                 buf.copy_(d)
             else:
@@ -369,14 +375,14 @@ class FusedOptimizer:
         else:
             m, v = self.m[lo:hi], self.v[lo:hi]
             t = float(self.step_t[i].item()) + 1.0
-            b1, b2 = self.betas
+            # the betas as the kernel receives them: fp32 values, and 1 - beta formed in fp32 (f32(1 - f32(0.999)) is
+            # 1.3e-5 away from 0.001)
+            f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))
+            b1, b2 = f32(self.betas[0]), f32(self.betas[1])
             if self.kind == "adamw":
                 p.mul_(1 - lr * self.weight_decay)
-                d = g
-            else:
-                d = g + self.weight_decay * p if self.weight_decay else g
-            m.mul_(b1).add_(d, alpha=1 - b1)
-            v.mul_(b2).addcmul_(d, d, value=1 - b2)
+            m.mul_(b1).add_(d, alpha=f32(1 - b1))
+            v.mul_(b2).addcmul_(d, d, value=f32(1 - b2))
             denom = (v.sqrt() / (1 - b2 ** t) ** 0.5).add_(self.eps)
             p.addcdiv_(m, denom, value=-lr / (1 - b1 ** t))
         self.step_t[i] += 1
