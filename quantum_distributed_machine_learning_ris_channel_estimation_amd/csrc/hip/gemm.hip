@@ -1314,9 +1314,10 @@ __global__ void __launch_bounds__(G::NT, 1) gemm_kernel(Args a) {
     __syncthreads();
     if (na.dYt8 != nullptr) {
       // the tile's dY (now in ct) transposed: column j -> 16-byte runs of dYt8 row j0 + j (lanes take consecutive
-      // columns: conflict-free LDS reads)
+      // columns: conflict-free LDS reads).  The stride is the compute waves' thread count: on a producer-wave tile
+      // the producers have ended, and a stride of NT left every other block of 64 NW items unwritten
       const int M = a.I;
-      for (int it = tid; it < G::BN * (G::BM / 16); it += G::NT) {
+      for (int it = tid; it < G::BN * (G::BM / 16); it += 64 * G::NW) {
         const int j = it % G::BN, g = it / G::BN;
         uint32_t w[4];
 #pragma unroll

@@ -38,9 +38,13 @@ REC = ("mean", "inv", "a", "b", "c1", "c2", "c3")
 
 # ------------------------------------------------------------------------------------------ number formats
 def round_bf16(x: torch.Tensor) -> torch.Tensor:
-    """float64 -> the nearest bf16 (ties to even), ONE rounding, as float64 (normal range; NaN stays NaN)."""
-    m, e = torch.frexp(x.to(D))
-    return torch.ldexp(torch.round(m * 256.0) / 256.0, e)
+    """float64 -> the nearest bf16 (ties to even), ONE rounding, as float64 (normal range; NaN stays NaN).  Integer
+    arithmetic on the bits -- the 45 low mantissa bits rounded away, half to even -- so it is exact on any device
+    (frexp / ldexp on the GPU gave 1159.9999999999998 for 1160)."""
+    x = x.to(D)
+    b = x.view(torch.int64)
+    r = (b + ((1 << 44) - 1) + ((b >> 45) & 1)) & ~((1 << 45) - 1)
+    return torch.where(torch.isnan(x), x, r.view(D))
 
 
 def is_bf16(x: torch.Tensor) -> bool:
