@@ -157,6 +157,10 @@ class EvalConfig:
     # of the evaluated chunk itself ("batch": removes a noisy device's per-wire affine distortion, but a prediction
     # then depends on the chunk it is in) or with the running statistics of training ("running")
     qsc_post_stats: str = "batch"
+    # test-time routing: "hard" (the reference: every sample through the arg-max expert of the classifier) or
+    # "soft" (additionally: the experts combined under the classifier's posterior, and the oracle routing by the true
+    # scenario -- the nmse_*_soft / nmse_oracle rows)
+    routing: str = "hard"
 
     def update_from_dict(self, d: Dict[str, Any]) -> "EvalConfig":
         names = {f.name for f in dataclasses.fields(self)}

@@ -46,6 +46,9 @@
 //             On the producer-wave forward tile (cfg 8) the producers prefetch the label rows during the K loop
 //             and run the row pass (NmsePrefetch): Y is rounded to bf16 first and the column sums come per chunk
 //             of 4 E rows, so dY and the bias gradient are bit-identical to the plain forward + that kernel.
+//   EPI_MIX   the inference forward over ALL experts' rows with the posterior-weighted combination of each
+//             sample's three product rows in the row pass: C[i] bf16 = sum_e p[i, e] acc[3 i + e] (+ bias)
+//             (qd_gemm_fwd_mix: soft test-time routing; the mix is in fp32, after the product)
 #include <type_traits>
 
 #include "common.h"
@@ -64,7 +67,7 @@ typedef __attribute__((address_space(1))) void glb_void;
 // stage): with a WM x 1 wave grid every A row belongs to exactly one wave, so staging A through LDS only
 // costs LDS bandwidth (round 4, see the DA configurations below)
 enum { KC = 0, MC = 1, MC8 = 2, KCD = 3 };
-enum { EPI_F32 = 0, EPI_BF16 = 1, EPI_NMSE = 2, EPI_ADAM = 3 };
+enum { EPI_F32 = 0, EPI_BF16 = 1, EPI_NMSE = 2, EPI_ADAM = 3, EPI_MIX = 4 };
 // (diagnosis builds: EPI_BF16 with the BN reduction epilogue's DBG = EPI - 4, see bnred_epilogue)
 enum { EPI_BF16_D1 = 5, EPI_BF16_D2 = 6, EPI_BF16_D3 = 7 };
 constexpr int BK = 64;
@@ -419,6 +422,11 @@ struct Stager {
   }
 };
 
+// EPI_MIX: p (I / 3, 3) fp32, the weights of the three product rows of every output row
+struct MixEpi {
+  const float* p;
+};
+
 struct Args {
   const uint16_t* P;
   const uint16_t* Q;
@@ -427,7 +435,10 @@ struct Args {
   void* C;              // fp32 (EPI_F32) or bf16 (EPI_BF16)
   int ldc;
   const uint16_t* bias; // EPI_BF16: per output column j, nullable
-  NmseArgs na;          // EPI_NMSE
+  union {               // the epilogue's own arguments (one slot: the kernels' argument block keeps its size)
+    NmseArgs na;        // EPI_NMSE
+    MixEpi mx;          // EPI_MIX
+  };
   const long* pexp;     // nullable: row i of P is P[i * pe + pexp[i]] (KC P only: expert-routed rows)
   int pe;
   const float* deq;     // nullable: (2,) dequantisation scales; the accumulators are multiplied by their product
@@ -1183,6 +1194,37 @@ __global__ void __launch_bounds__(G::NT, 1) gemm_kernel(Args a) {
             (uint32_t)f32_to_bf16(v.x + bv[0]) | ((uint32_t)f32_to_bf16(v.y + bv[1]) << 16);
       }
     }
+  } else if constexpr (EPI == EPI_MIX) {
+    // Tile rows 3 s + e are the three experts' products of output row i0 / 3 + s (a tile of BM % 3 == 0 rows holds
+    // whole samples, as in the training epilogues' 3-expert fast paths): one output row per wave pass,
+    // y = fma(p2, acc2, fma(p1, acc1, p0 acc0)) in fp32, then bias and rounding as EPI_BF16.  With a one-hot p the
+    // chain returns the selected accumulator unchanged (1 acc + 0 finite is exact), i.e. the routed forward's row.
+    static_assert(G::BM % 3 == 0 && G::KS == 1 && G::F8 == 0, "whole 3-expert samples per tile, bf16 operands");
+    uint16_t* C = reinterpret_cast<uint16_t*>(a.C);
+    float bv[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) bv[v] = a.bias ? bf16_to_f32(a.bias[j0 + c0 + v]) : 0.f;
+    const float* pw3 = a.mx.p + i0;   // (3 (i0 / 3) = i0)
+    for (int s = __builtin_amdgcn_readfirstlane(wave); s < G::BM / 3; s += G::NW) {
+      const float p0 = pw3[3 * s], p1 = pw3[3 * s + 1], p2 = pw3[3 * s + 2];
+      const float* src = ct + 3 * s * PITCH + c0;
+      uint16_t* dst = C + (size_t)(i0 / 3 + s) * a.ldc + j0 + c0;
+      using VT = std::conditional_t<VEC == 4, float4, float2>;
+      const VT v0 = *reinterpret_cast<const VT*>(src), v1 = *reinterpret_cast<const VT*>(src + PITCH),
+               v2 = *reinterpret_cast<const VT*>(src + 2 * PITCH);
+      const float *x0 = &v0.x, *x1 = &v1.x, *x2 = &v2.x;
+      float m[VEC];
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) m[v] = __builtin_fmaf(p2, x2[v], __builtin_fmaf(p1, x1[v], p0 * x0[v])) + bv[v];
+      if constexpr (VEC == 4) {
+        uint2 w;
+        w.x = (uint32_t)f32_to_bf16(m[0]) | ((uint32_t)f32_to_bf16(m[1]) << 16);
+        w.y = (uint32_t)f32_to_bf16(m[2]) | ((uint32_t)f32_to_bf16(m[3]) << 16);
+        *reinterpret_cast<uint2*>(dst) = w;
+      } else {
+        *reinterpret_cast<uint32_t*>(dst) = (uint32_t)f32_to_bf16(m[0]) | ((uint32_t)f32_to_bf16(m[1]) << 16);
+      }
+    }
   } else {
     static_assert(EPI != EPI_NMSE || VEC == 2, "the NMSE epilogue walks 128-column tiles");
     // HDCE loss: per-stream coefficients of the streams this tile touches (den_s summed over the
@@ -1477,6 +1519,28 @@ QD_API int qd_gemm_fwd_bias(const uint16_t* A, const uint16_t* W, const uint16_t
   if (cfg == 101) return launch<Geo<9, 2, 1, 4, KC, KC, 4, 1>, EPI_BF16, 4, 8>(a, st);   // (diagnosis builds)
   if (cfg == 102) return launch<Geo<9, 2, 1, 4, KC, KC, 4, 2>, EPI_BF16, 4, 8>(a, st);
   return launch<FwdA, EPI_BF16, 4, 8>(a, st);
+}
+
+// Soft test-time routing: Y (M, N) bf16 = sum_e P[i, e] (A[i E + e] . W^T) (+ bias), the posterior-weighted
+// combination of every sample's expert rows (EPI_MIX; the shared FC is linear, so this is the MMSE combination of
+// the expert estimates).  A (M E, K) bf16 rows (i, e) -- the layout the conv stack writes and the routed forward
+// reads --, W (N, K) bf16, bias (N) bf16 nullable, P (M, E) fp32.  The dense product over all M E rows runs on the
+// MFMAs (three times the routed forward's work); the mix is in fp32 on the accumulators:
+//   Y[i, j] = bf16(fma(P[i, 2], acc[3 i + 2, j], fma(P[i, 1], acc[3 i + 1, j], P[i, 0] acc[3 i, j])) + bias[j])
+// so a one-hot P gives qd_gemm_fwd_bias's routed rows bit for bit.
+// Rules (anything else: hipErrorInvalidValue before any launch, Y untouched):
+//   E == 3;  cfg 0 or 8 (the 144 x 128 tiles, 48 whole samples each; cfg 8 = producer waves) -- the direct-A tile
+//   (cfg 5) is refused as for routed rows, the other tiles are not instantiated;  the cfg must tile the DENSE
+//   product as qd_gemm_fwd_ok says: (M E) % 144 == 0, i.e. M % 48 == 0, N % 128 == 0, K % 64 == 0, K >= 64.
+QD_API int qd_gemm_fwd_mix(const uint16_t* A, const uint16_t* W, const uint16_t* bias, const float* P, uint16_t* Y,
+                           int M, int N, int K, int E, int cfg, void* stream) {
+  if (E != 3 || (cfg != 0 && cfg != 8) || !A || !W || !P || !Y || M < 1 || M > (1 << 29)) return (int)hipErrorInvalidValue;
+  if (!qd_gemm_fwd_ok(M * E, N, K, cfg) || K < BK) return (int)hipErrorInvalidValue;
+  Args a{A, W, K, K, M * E, N, K, Y, N, bias, {}, nullptr, 0, nullptr};
+  a.mx = MixEpi{P};
+  hipStream_t st = (hipStream_t)stream;
+  if (cfg == 8) return launch<FwdQ, EPI_MIX, 4, 8>(a, st);
+  return launch<FwdA, EPI_MIX, 4, 8>(a, st);
 }
 
 // The training forward with the HDCE-loss epilogue (see the header).  rows M = U*B*E in (u, b, e)

@@ -61,6 +61,30 @@ def gemm_fwd(A: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor] = None,
     return Y
 
 
+def gemm_fwd_mix(A: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor], weights: torch.Tensor,
+                 out: Optional[torch.Tensor] = None, cfg: int = 0) -> torch.Tensor:
+    """Y[i] = sum_e weights[i, e] (A[i * E + e] W^T) (+ b), bf16: the posterior-weighted combination of every
+    sample's expert rows in the forward GEMM's epilogue (csrc/hip/gemm.hip qd_gemm_fwd_mix; soft test-time
+    routing).  A (>= M E, K) bf16 rows (i, e) as for ``gemm_fwd``'s routed rows, W (N, K) bf16, ``weights`` (M, E)
+    fp32.  The mix is in fp32 on the accumulators: one-hot weights give ``gemm_fwd(..., expert=)`` bit for bit.
+    E == 3, cfg 0 or 8, and the cfg must tile the dense (M E, N, K) product (M % 48 == 0); anything else raises
+    RuntimeError before any launch."""
+    assert weights.dim() == 2 and weights.dtype == torch.float32 and weights.is_contiguous()
+    assert weights.device == A.device
+    M, E = weights.shape
+    K = A.shape[1]
+    N = W.shape[0]
+    assert A.shape[0] >= M * E
+    assert A.dtype == W.dtype == torch.bfloat16 and A.is_contiguous() and W.is_contiguous() and W.shape[1] == K
+    assert b is None or (b.dtype == torch.bfloat16 and b.numel() == N and b.is_contiguous())
+    Y = out if out is not None else torch.empty(M, N, device=A.device, dtype=torch.bfloat16)
+    assert Y.dtype == torch.bfloat16 and Y.shape[0] >= M and Y.shape[1] == N and Y.is_contiguous()
+    f = _gemm_fn("qd_gemm_fwd_mix", [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p])
+    nat.check(f(nat.ptr(A), nat.ptr(W), nat.ptr(b) if b is not None else None, nat.ptr(weights), nat.ptr(Y), M, N, K,
+                E, cfg, nat.stream_ptr(A.device)), "gemm_fwd_mix")
+    return Y
+
+
 def gemm_wgrad(dY: torch.Tensor, A: torch.Tensor, out: Optional[torch.Tensor] = None, cfg: int = 0) -> torch.Tensor:
     """dW = dY^T A in fp32 (dY (M, N), A (M, K) bf16 row-major; the reduction runs over M)."""
     M, N = dY.shape

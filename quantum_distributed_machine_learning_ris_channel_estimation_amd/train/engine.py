@@ -259,6 +259,25 @@ def estimate_routed(convs: Sequence[nn.Module], fc: nn.Module, x: torch.Tensor, 
     return out
 
 
+@torch.no_grad()
+def estimate_mixed(convs: Sequence[nn.Module], fc: nn.Module, x: torch.Tensor, weights: torch.Tensor,
+                   chunk: int = 4096) -> torch.Tensor:
+    """Soft test-time routing: sum_e weights[:, e, None] * fc(conv_e(x)), every expert on every sample.
+
+    With ``weights`` the scenario classifier's posterior this is the MMSE combination of the expert
+    estimates (the shared CE is linear); one-hot weights give ``estimate_routed``.  ``weights`` is (N, E)."""
+    E = len(convs)
+    if weights.dim() != 2 or tuple(weights.shape) != (x.shape[0], E):
+        raise ValueError(f"weights must be ({x.shape[0]}, {E}), got {tuple(weights.shape)}")
+    w = weights.to(x.device, torch.float32)
+    out = torch.zeros(x.shape[0], fc.FC.out_features, device=x.device, dtype=torch.float32)
+    for s in range(0, x.shape[0], chunk):
+        xs = x[s:s + chunk].float()
+        for e in range(E):
+            out[s:s + chunk] += w[s:s + chunk, e, None] * fc(convs[e](xs)).float()
+    return out
+
+
 class HDCEStep:
     """One fused HDCE training step over 9 stream batches (see module docstring).
 

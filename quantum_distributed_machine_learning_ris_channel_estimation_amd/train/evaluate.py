@@ -29,7 +29,7 @@ from ..data.baselines import lmmse_estimate
 from ..data.channel import generate_mixed, pack_channel, pack_pilots
 from ..models.estimators import Conv_P128, FC_P128, NMSELoss, QSC_P128, SC_P128
 from . import checkpoint as ck
-from .engine import estimate_routed
+from .engine import estimate_mixed, estimate_routed
 
 
 @torch.no_grad()
@@ -81,6 +81,10 @@ def _epoch_file(d: str, pattern_fmt: str, prefer: str) -> Optional[str]:
     return best
 
 
+ROUTINGS = ("hard", "soft")
+SOFT_KEYS = ("nmse_classical_soft", "nmse_quantum_soft", "nmse_oracle")   # evaluate_snr's extra rows of "soft"
+
+
 class model_val:
     def __init__(self, cfg: Optional[EvalConfig] = None, **overrides):
         cfg = cfg or EvalConfig()
@@ -95,6 +99,7 @@ class model_val:
         self._qsc_noise = None
         self.qsc_noise_model()   # (refuses noise rates without qsc_shots)
         self._post_stats()
+        self._routing()
         self.results: Dict[str, List[float]] = {}
 
     def load_model_state_dict(self, model, filepath, fallback_key=None):
@@ -118,6 +123,11 @@ class model_val:
         if str(self.qsc_post_stats) not in STATS:
             raise ValueError(f"unknown qsc_post_stats {self.qsc_post_stats!r}: one of {STATS}")
         return str(self.qsc_post_stats)
+
+    def _routing(self) -> str:
+        if self.routing not in ROUTINGS:
+            raise ValueError(f"unknown routing {self.routing!r}: one of {ROUTINGS}")
+        return self.routing
 
     # ------------------------------------------------------------------ loading
     def _dir(self) -> str:
@@ -187,10 +197,21 @@ class model_val:
         out = {"nmse_ls": float(criterion(pack_channel(HLS), perf)),
                "nmse_mmse": float(criterion(pack_channel(HMMSE), perf)),
                "nmse_lmmse": float(criterion(pack_channel(HLMMSE), perf))}
+        soft = self._routing() == "soft"
+        if soft:
+            for clf in (sc, qsc):
+                nc = None if clf is None else clf.FC.out_features if isinstance(clf, SC_P128) else clf.n_classes
+                if nc is not None and nc != len(convs):
+                    raise ValueError(f"soft routing: a classifier of {nc} classes cannot weight {len(convs)} experts")
         eng = self._hip_engine(sc, qsc, convs, fc)
+        if soft:   # the oracle row: hard routing by the true scenario
+            Hor = eng.estimate(x, ind) if eng is not None else estimate_routed(convs, fc, x, ind.to(x.device))
+            out["nmse_oracle"] = float(criterion(Hor, perf))
         for tag, clf in (("classical", sc), ("quantum", qsc)):
             if clf is None:
                 out[f"nmse_{tag}"], out[f"acc_{tag}"] = float("nan"), float("nan")
+                if soft:
+                    out[f"nmse_{tag}_soft"] = float("nan")
                 continue
             # qsc_shots > 0: the quantum SC's circuit is measured with that many shots per sample (seeded by cfg.seed)
             shots = int(self.qsc_shots) if tag == "quantum" and getattr(clf, "use_quantum", False) else 0
@@ -198,8 +219,9 @@ class model_val:
             traj = int(self.qsc_trajectories) if noise is not None else 1
             if eng is not None and (eng.sc if tag == "classical" else eng.qsc) is not None:
                 # the HIP kernels: classifier, experts, routed FC (train/infer.py)
-                pred = (eng.classify(x, tag, shots=shots, seed=self.seed, noise=noise, trajectories=traj) if shots
-                        else eng.classify(x, tag))
+                pred = (eng.classify(x, tag, shots=shots, seed=self.seed, noise=noise, trajectories=traj,
+                                     return_logp=soft) if shots else eng.classify(x, tag, return_logp=soft))
+                pred, logp = pred if soft else (pred, None)
             else:   # (CPU, or the classical-fallback QSC ablation: torch)
                 if shots:
                     ql = clf.qlayer
@@ -207,7 +229,8 @@ class model_val:
                     ql.shots, ql.noise, ql.trajectories = shots, noise, traj
                     ql.manual_shot_seed(self.seed)
                 try:
-                    pred = torch.cat([clf(x[i:i + chunk]).argmax(1) for i in range(0, x.shape[0], chunk)])
+                    logp = torch.cat([clf(x[i:i + chunk]) for i in range(0, x.shape[0], chunk)])
+                    pred = logp.argmax(1)
                 finally:
                     if shots:
                         ql.shots, ql.shot_seed, ql._shot_calls, ql.noise, ql.trajectories = exact
@@ -220,6 +243,10 @@ class model_val:
                 Hhat = eng.estimate(x, pred)
             else:
                 Hhat = estimate_routed(convs, fc, x, pred)
+            if soft:   # the experts under the posterior the prediction was the arg-max of (same shots, noise, seed)
+                wts = logp.float().exp()
+                Hs = eng.estimate_mixed(x, wts) if eng is not None else estimate_mixed(convs, fc, x, wts)
+                out[f"nmse_{tag}_soft"] = float(criterion(Hs, perf))
             if saved is not None:
                 restore_bn(convs, saved)
                 if eng is not None:
@@ -258,6 +285,9 @@ class model_val:
             r = self.evaluate_snr(float(snr), sc, qsc, convs, fc)
             for k in keys:
                 res[k].append(r[k])
+            for k in SOFT_KEYS:   # (routing="soft")
+                if k in r:
+                    res.setdefault(k, []).append(r[k])
             db = lambda v: 10 * np.log10(v)
             print(f"SNR {snr}dB Results:")
             print(f"  LS NMSE: {db(r['nmse_ls']):.2f} dB")
@@ -269,15 +299,18 @@ class model_val:
             print(f"  SC Accuracy (Classical): {r['acc_classical']:.4f}")
             if qsc is not None:
                 print(f"  SC Accuracy (Quantum): {r['acc_quantum']:.4f}")
+            for k in SOFT_KEYS:
+                if k in r and r[k] == r[k]:
+                    print(f"  {k}: {db(r[k]):.2f} dB")
         self.results = res
         self.create_comparison_plots(SNRdb, res["nmse_ls"], res["nmse_mmse"], res["nmse_classical"],
                                      res["nmse_quantum"], res["acc_classical"], res["acc_quantum"],
-                                     nmse_lmmse=res["nmse_lmmse"])
+                                     nmse_lmmse=res["nmse_lmmse"], soft={k: res[k] for k in SOFT_KEYS if k in res})
         return 0
 
     # ------------------------------------------------------------------ reporting
     def create_comparison_plots(self, SNRdb, nmse_ls, nmse_mmse, nmse_classical, nmse_quantum, acc_classical,
-                                acc_quantum, nmse_lmmse=None):
+                                acc_quantum, nmse_lmmse=None, soft=None):
         os.makedirs(self.results_dir, exist_ok=True)
         db = lambda xs: [10 * np.log10(x) if x == x else float("nan") for x in xs]
         results = {
@@ -295,6 +328,8 @@ class model_val:
         }
         if nmse_lmmse is not None:
             results["NMSE_LMMSE_dB"] = db(nmse_lmmse)
+        for k, v in (soft or {}).items():   # routing="soft": NMSE_HDCE_Classical_Soft_dB, ..._Quantum_Soft_dB, ..._Oracle_dB
+            results["NMSE_HDCE_" + "_".join(w.capitalize() for w in k.split("_")[1:]) + "_dB"] = db(v)
         with open(os.path.join(self.results_dir, "quantum_classical_comparison.json"), "w") as f:
             json.dump(results, f, indent=4)
         try:

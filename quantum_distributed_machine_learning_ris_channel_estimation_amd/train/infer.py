@@ -14,6 +14,8 @@ Here, per chunk of ``chunk`` samples (one static buffer set; graph-friendly, no 
               experts densely costs less than sorting samples into buckets
   routed FC   csrc/hip/gemm.hip forward GEMM whose A-operand loads read row ``i * E + expert[i]`` of the
               expert features: the top-1 routing is fused into the GEMM (no permutation, no scatter)
+  mixed FC    (soft routing) the same GEMM over ALL expert rows, the classifier's posterior combining each
+              sample's three product rows in its epilogue (``estimate_mixed``, csrc/hip/gemm.hip EPI_MIX)
 """
 from __future__ import annotations
 
@@ -69,6 +71,8 @@ class HIPInference:
         self.idx = torch.zeros(chunk, dtype=torch.int64, device=self.dev)
         self.pred = torch.zeros(chunk, dtype=torch.int64, device=self.dev)
         self.Y = torch.empty(chunk, self.W_lp.shape[0], device=self.dev, dtype=torch.bfloat16)
+        self.wmix = torch.zeros(chunk, self.E, device=self.dev)    # (estimate_mixed's weights of the chunk)
+        self._logp = {}                                             # (classify(return_logp=True): per classifier)
         self._gather = nat.fn(nat.hip_lib(), "qd_gather_step", [_p, _p, _l, _p, _p, _p, _l, _i, _i, _i, _i, _p])
         self._plane = plane
 
@@ -159,8 +163,10 @@ class HIPInference:
 
     @torch.no_grad()
     def classify(self, x: torch.Tensor, which: str, shots: int = 0, seed: int = 0, noise=None,
-                 trajectories: int = 1) -> torch.Tensor:
+                 trajectories: int = 1, return_logp: bool = False):
         """Predicted scenario (N,) int64 of every sample with the classical ("classical") or quantum SC.
+        ``return_logp``: ``(pred, logp)`` with the log-posterior (N, n_classes) fp32 of the same launches -- under
+        ``shots`` / ``noise`` the one of the measured <Z_i>, exactly what ``pred`` was taken from.
         ``shots`` > 0 ("quantum" only): the circuit is measured with that many shots per sample; the shot
         stream is keyed by ``seed`` and the chunk index (the counter), the sample's row within its chunk.
         ``noise`` / ``trajectories`` (with ``shots``): measured under that ``ops.quantum.NoiseModel``."""
@@ -173,20 +179,30 @@ class HIPInference:
         x = x.contiguous().float()
         N = x.shape[0]
         out = torch.empty(N, dtype=torch.int64, device=self.dev)
+        lp = lbuf = None
+        if return_logp:
+            C = 3 if which == "classical" else self.qsc.C
+            lp = torch.empty(N, C, device=self.dev)
+            if which == "quantum":
+                lbuf = self._logp.setdefault(C, torch.zeros(self.chunk, C, device=self.dev))
         for lo in range(0, N, self.chunk):
             n = min(self.chunk, N - lo)
             self._load(x, lo, n)
             if which == "classical":
-                self.sc.forward(self.xq, self.pred)
+                lbuf = self.sc.forward(self.xq, self.pred)
             else:
-                self.qsc.infer(self.xq, self.pred, shots=shots, seed=seed, counter=lo // self.chunk, noise=noise,
-                               trajectories=trajectories, valid=n)
+                self.qsc.infer(self.xq, self.pred, logp=lbuf, shots=shots, seed=seed, counter=lo // self.chunk,
+                               noise=noise, trajectories=trajectories, valid=n)
             out[lo:lo + n].copy_(self.pred[:n])
-        return out
+            if return_logp:
+                lp[lo:lo + n].copy_(lbuf[:n])
+        return (out, lp) if return_logp else out
 
     @torch.no_grad()
     def estimate(self, x: torch.Tensor, expert: torch.Tensor) -> torch.Tensor:
-        """Routed estimate (N, 2048) fp32: sample i through expert ``expert[i]`` and the shared FC."""
+        """Routed estimate (N, 2048) fp32: sample i through expert ``expert[i]`` and the shared FC.  Every
+        expert's conv stack runs on every sample by design (see the module docstring); ``estimate_mixed`` relies
+        on it: its GEMM reads all the rows (b, e) this one selects from."""
         from ..ops.fc import gemm_fwd
         x = x.contiguous().float()
         N = x.shape[0]
@@ -198,5 +214,29 @@ class HIPInference:
             self.pred[:n].copy_(expert[lo:lo + n])
             h = self.conv.forward(self.x1, training=False)            # (chunk * E, 32 H W) bf16, rows (b, e)
             gemm_fwd(h, self.W_lp, self.b_lp, out=self.Y, expert=self.pred, n_experts=self.E)
+            out[lo:lo + n].copy_(self.Y[:n])
+        return out
+
+    @torch.no_grad()
+    def estimate_mixed(self, x: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+        """Soft-routed estimate (N, 2048) fp32: sum_e weights[i, e] * (expert e of sample i through the shared
+        FC), the combination in the FC GEMM's epilogue (ops.fc.gemm_fwd_mix; the bias is added once, so this is
+        ``engine.estimate_mixed`` for weights that sum to 1).  ``weights`` (N, E) fp32, e.g. ``exp(logp)`` of
+        ``classify(..., return_logp=True)``.  The chunk must be a multiple of 48 (whole GEMM tiles)."""
+        from ..ops.fc import gemm_fwd_mix
+        x = x.contiguous().float()
+        N = x.shape[0]
+        if weights.dim() != 2 or tuple(weights.shape) != (N, self.E):
+            raise ValueError(f"weights must be ({N}, {self.E}), got {tuple(weights.shape)}")
+        weights = weights.to(self.dev, torch.float32)
+        out = torch.empty(N, self.W_lp.shape[0], device=self.dev)
+        for lo in range(0, N, self.chunk):
+            n = min(self.chunk, N - lo)
+            self._load(x, lo, n)
+            self.wmix[:n].copy_(weights[lo:lo + n])
+            if n < self.chunk:   # (the tail repeats sample lo, as _load's: its outputs are dropped)
+                self.wmix[n:].copy_(weights[lo:lo + 1].expand(self.chunk - n, self.E))
+            h = self.conv.forward(self.x1, training=False)            # (chunk * E, 32 H W) bf16, rows (b, e)
+            gemm_fwd_mix(h, self.W_lp, self.b_lp, self.wmix, out=self.Y)
             out[lo:lo + n].copy_(self.Y[:n])
         return out

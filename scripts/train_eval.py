@@ -30,6 +30,8 @@ def main():
                     "(written under <out>/bn_adapt)")
     ap.add_argument("--swa-epochs", type=int, default=0, help="also average the HDCE weights over the last K epochs "
                     "and run the sweep on the average (written under <out>/swa, and <out>/swa_bn_adapt with --bn-adapt)")
+    ap.add_argument("--routing", default="hard", choices=["hard", "soft"], help="soft: the sweeps also report the "
+                    "posterior-weighted (nmse_*_soft) and oracle-routed (nmse_oracle) rows")
     a = ap.parse_args()
     from quantum_distributed_machine_learning_ris_channel_estimation_amd.train.evaluate import model_val
     from quantum_distributed_machine_learning_ris_channel_estimation_amd.train.runner import Y2HRunner
@@ -60,14 +62,15 @@ def main():
         json.dump(hist, f, indent=1)
     plot_fig2(curves, os.path.join(a.out, "loss_curve.png"))
     mv = model_val(workspace=a.workspace, results_dir=a.out, data_len_for_test=a.test_len,
-                   training_data_len=a.data_len, batch_size_DML=a.batch, n_qubits=a.qubits)
+                   training_data_len=a.data_len, batch_size_DML=a.batch, n_qubits=a.qubits, routing=a.routing)
     mv.epoch_tag = f"epoch{a.epochs - 1}"
     t0 = time.time()
     mv.test_for_CE_P128_for_all_scenarios()
     t["eval_s"] = time.time() - t0
     if a.bn_adapt:
         mva = model_val(workspace=a.workspace, results_dir=os.path.join(a.out, "bn_adapt"), data_len_for_test=a.test_len,
-                        training_data_len=a.data_len, batch_size_DML=a.batch, n_qubits=a.qubits, bn_adapt=True)
+                        training_data_len=a.data_len, batch_size_DML=a.batch, n_qubits=a.qubits, bn_adapt=True,
+                        routing=a.routing)
         mva.epoch_tag = mv.epoch_tag
         t0 = time.time()
         mva.test_for_CE_P128_for_all_scenarios()
@@ -75,7 +78,7 @@ def main():
     if a.swa_epochs > 0:
         for sub, bn in (("swa", False),) + ((("swa_bn_adapt", True),) if a.bn_adapt else ()):
             mvs = model_val(workspace=a.workspace, results_dir=os.path.join(a.out, sub), data_len_for_test=a.test_len,
-                            training_data_len=a.data_len, batch_size_DML=a.batch, n_qubits=a.qubits, bn_adapt=bn,
+                            training_data_len=a.data_len, batch_size_DML=a.batch, n_qubits=a.qubits, bn_adapt=bn, routing=a.routing,
                             hdce_tag="swa")
             mvs.epoch_tag = mv.epoch_tag
             t0 = time.time()
