@@ -14,10 +14,11 @@
 // model's flat gradient layout -> one deterministic column-sum adds it into the flat buffer.
 // The backward kernel recomputes the forward activations of its sample instead of storing
 // them (cheaper than the HBM round trip).
-#include "common.h"
+#include "qsim_gates.h"   // hash_normal: the weight-noise stream
 
 namespace qd {
 namespace qsc {
+using qd::hash_normal;
 
 constexpr int C1 = 16, C2 = 32;
 constexpr int NT = 256;
@@ -491,20 +492,6 @@ __global__ void __launch_bounds__(1024) qsc_head_kernel(const float* __restrict_
 // device counter is read by every thread and then advanced by thread 0, so every replay draws
 // fresh noise, and forward and backward of the same step see the same noisy weights.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z += 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ float hash_normal(unsigned long long seed, unsigned long long ctr, unsigned int i) {
-  const unsigned long long h = mix64(seed ^ mix64(ctr * 0x100000001b3ull + i));
-  const float u1 = ((h >> 40) + 1u) * (1.0f / 16777217.0f);          // (0, 1]
-  const float u2 = ((h >> 16) & 0xffffffu) * (1.0f / 16777216.0f);   // [0, 1)
-  return sqrtf(-2.f * __logf(u1)) * __cosf(6.283185307179586f * u2);
-}
-
 __global__ void __launch_bounds__(256) qnoise_kernel(const float* __restrict__ w, float* __restrict__ out, int G,
                                                      int P, float sigma, unsigned long long seed,
                                                      unsigned long long* __restrict__ counter) {

@@ -24,16 +24,15 @@
 //    weight grads are accumulated per lane in LDS over all samples a wave owns and
 //    written as one slab row per wave (deterministic, no float atomics); the slab
 //    is summed by qsim_reduce_slab (or by the fused optimizer).
-#include "common.h"
+#include "qsim_gates.h"
 
 namespace qd {
 namespace qsim {
+using qd::cf;
+using qd::cmul;
+using qd::ring_fwd;
+using qd::ring_inv;
 
-struct cf {
-  float x, y;
-};
-
-__device__ __forceinline__ cf cmul(cf a, cf b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 __device__ __forceinline__ cf cscale(cf a, float s) { return {a.x * s, a.y * s}; }
 
 template <int N>
@@ -46,23 +45,6 @@ struct Cfg {
   static constexpr int SPW = kWave / LPS;       // samples per wave
   static constexpr int SLOTS = kWave * R;       // complex slots per wave (= SPW * D)
 };
-
-// f(k): basis-state map of the CNOT ring (CNOT(0,1) first ... CNOT(n-1,0) last).
-template <int N>
-__device__ __forceinline__ int ring_fwd(int k) {
-#pragma unroll
-  for (int i = 0; i < N - 1; ++i) k ^= ((k >> i) & 1) << (i + 1);
-  k ^= (k >> (N - 1)) & 1;
-  return k;
-}
-// f^-1(k): the same self-inverse CNOTs in reverse order.
-template <int N>
-__device__ __forceinline__ int ring_inv(int k) {
-  k ^= (k >> (N - 1)) & 1;
-#pragma unroll
-  for (int i = N - 2; i >= 0; --i) k ^= ((k >> i) & 1) << (i + 1);
-  return k;
-}
 
 // Apply the ring permutation (or its inverse) to a wave's states through LDS.
 // `lds` is this wave's SLOTS-entry region; `sbase` = sample-in-wave * D.

@@ -32,45 +32,22 @@
 // (32 KiB per state; the backward holds psi and lambda: 2 workgroups per CU).  Outputs match qsim_big.hip:
 // E (B, 12); dx (B, 12); slab (gridDim.x, 2 n L) per-workgroup dW partials in a fixed sample order (summed by
 // the caller); psave (B, 2, 4096) fp32 planes, written by the forward, read by the backward.
-#include "common.h"
+#include "qsim_mfma_dev.h"
 
 namespace qd {
 namespace qm12 {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 h8;
-typedef __attribute__((ext_vector_type(4))) float f4;
+using namespace qd::qmdev;
+using qd::cf;
+using qd::cmul;
+using qd::ring_fwd;
 
 constexpr int N = 12;
 constexpr int D = 1 << N;
 constexpr int NT = 256;
-constexpr float LO_SCALE = 2048.f, LO_INV = 1.f / 2048.f;
 // operand image of one (group, layer >= 1, mode, direction): [form r / i][hi / lo][lane] h8
 constexpr int IMG_H8 = 2 * 2 * 64;
 // per (group, layer >= 1): 3 modes x {forward, adjoint}
 constexpr int LAYER_H8 = 3 * 2 * IMG_H8;
-
-struct cf {
-  float x, y;
-};
-__device__ __forceinline__ cf cmul(cf a, cf b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-
-// R = RZ(phi) RY(theta) entry [a][b] from (cos, sin) of theta / 2 and of phi / 2 (qsim_mfma.hip's rot)
-__device__ __forceinline__ cf rot(float4 t, int a, int b) {
-  const float m = (a == b) ? t.x : (a == 0 ? -t.y : t.y);
-  return a == 0 ? cf{m * t.z, -m * t.w} : cf{m * t.z, m * t.w};
-}
-// (R_{q0+3} (x) .. (x) R_{q0})[a][b], 4-bit row / column
-__device__ __forceinline__ cf kron4(const float4* tr, int q0, int a, int b) {
-  cf v = {1.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) v = cmul(v, rot(tr[q0 + i], (a >> i) & 1, (b >> i) & 1));
-  return v;
-}
-__device__ __forceinline__ void split(float v, _Float16& hi, _Float16& lo) {
-  hi = (_Float16)v;
-  lo = (_Float16)((v - (float)hi) * LO_SCALE);
-}
-__device__ __forceinline__ f4 mfma(h8 a, h8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 
 // 8 floats -> fp16 hi / lo operands in pairs: hi = the packed round-toward-zero convert of two values, lo = the
 // exact residual v - hi (hi converted back) times 2^11, packed the same way -- two values per convert and no
@@ -93,14 +70,6 @@ __device__ __forceinline__ void split8(const float (&v)[8], h8& hi, h8& lo) {
 // LDS plane address of amplitude k: one float of padding per 16 (a 17-float row; pad()), so the strided operand reads of
 // all three modes are at most 2-way bank conflicts (8-way on the unpadded mode-0 reads)
 __device__ __forceinline__ int pad(int k) { return k + (k >> 4); }
-
-// CNOT ring CNOT(0,1) .. CNOT(n-2,n-1), CNOT(n-1,0) as a basis map, and its inverse (qsim_big.hip's)
-__device__ __forceinline__ int ring_fwd(int k) {
-#pragma unroll
-  for (int i = 0; i < N - 1; ++i) k ^= ((k >> i) & 1) << (i + 1);
-  k ^= (k >> (N - 1)) & 1;
-  return k;
-}
 
 // state index of mode index `e` (0..15) of mode M with the other two modes' index o (0..255, in k order)
 template <int M>
@@ -215,7 +184,7 @@ __device__ __forceinline__ void mode_apply(float* pr, float* pi, const Op& A, in
     for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int k = pad(ring_fwd(sidx<M>((wv * 4 + tt) * 16 + jj, 4 * gq + r)));
+        const int k = pad(ring_fwd<N>(sidx<M>((wv * 4 + tt) * 16 + jj, 4 * gq + r)));
         pr[k] = yr[tt][r];
         pi[k] = yi[tt][r];
       }
@@ -243,7 +212,7 @@ __device__ __forceinline__ void layer0(float* pr, float* pi, cf* tab, const floa
   for (int i = 0; i < D / NT; ++i) {
     const int k = tid + NT * i;
     const cf v = cmul(cmul(tab[k & 15], tab[16 + ((k >> 4) & 15)]), tab[32 + (k >> 8)]);
-    const int j = pad(ring_fwd(k));
+    const int j = pad(ring_fwd<N>(k));
     pr[j] = v.x;
     pi[j] = v.y;
   }
@@ -397,7 +366,7 @@ __global__ void __launch_bounds__(NT, 2) bwd_kernel(const float* __restrict__ x,
         float v[4][D / NT];
 #pragma unroll
         for (int i = 0; i < D / NT; ++i) {
-          const int j = pad(ring_fwd(tid + NT * i));
+          const int j = pad(ring_fwd<N>(tid + NT * i));
           v[0][i] = pr[j];
           v[1][i] = pi[j];
           v[2][i] = lr[j];

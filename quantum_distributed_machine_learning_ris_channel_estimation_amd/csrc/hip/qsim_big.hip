@@ -19,15 +19,18 @@
 // gathers psi and lambda from f(k) (inverse ring) and undoes the high rotations, the low pass
 // undoes the low ones; lambda = (sum_q g_q Z_q) psi is formed on the fly in the first reverse pass.
 // Per-gate gradient partials stay in registers across tiles and are block-reduced once per pass.
-#include "common.h"
+#include "qsim_gates.h"
 
 namespace qd {
 namespace qsimbig {
-
-struct cf {
-  float x, y;
-};
-__device__ __forceinline__ cf cmul(cf a, cf b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+using qd::cf;
+using qd::cmul;
+using qd::gate_adj;
+using qd::gate_fwd;
+using qd::ins_bits;
+using qd::layer_trig;
+using qd::ring_fwd;
+using qd::ring_inv;
 
 constexpr int NT = 256;   // 4 waves: lets the backward use AGPRs instead of scratch (512-thread groups spilled)
 // waves per SIMD the register allocation must allow (launch-bounds hint; the n <= 12 LDS state fits 4 forward /
@@ -55,61 +58,6 @@ struct G {
 // layer-0 scratch (2n <= 32) | phase table PI (n <= 12: <= 16 complex) | data (tiles, or the whole state
 // when n <= 12).
 constexpr int O_RED = 0, O_TRIG = 2048, O_G = 2304, O_ACC = 2368, O_TMP = 3392, O_PHI = 3584, O_DATA = 3712;
-
-template <int N>
-__device__ __forceinline__ int ring_fwd(int k) {
-#pragma unroll
-  for (int i = 0; i < N - 1; ++i) k ^= ((k >> i) & 1) << (i + 1);
-  k ^= (k >> (N - 1)) & 1;
-  return k;
-}
-template <int N>
-__device__ __forceinline__ int ring_inv(int k) {
-  k ^= (k >> (N - 1)) & 1;
-#pragma unroll
-  for (int i = N - 2; i >= 0; --i) k ^= ((k >> i) & 1) << (i + 1);
-  return k;
-}
-
-// insert NB zero bits at position P into t
-template <int P, int NB>
-__device__ __forceinline__ int ins_bits(int t) {
-  return ((t >> P) << (P + NB)) | (t & ((1 << P) - 1));
-}
-
-// Per-qubit trig of one layer, (cos, sin) of theta/2 and (cos, sin) of phi/2, into LDS.
-__device__ __forceinline__ void layer_trig(float4* trig, const float* wl, const float* xs, int n) {
-  if (threadIdx.x < n) {
-    const int q = threadIdx.x;
-    float s, c, sp, cp;
-    __sincosf(0.5f * (wl[2 * q] + (xs ? xs[q] : 0.f)), &s, &c);
-    __sincosf(0.5f * wl[2 * q + 1], &sp, &cp);
-    trig[q] = make_float4(c, s, cp, sp);
-  }
-}
-
-// forward gate RZ(phi) RY(theta) on the pair (a0: bit 0, a1: bit 1)
-__device__ __forceinline__ void gate_fwd(cf& a0, cf& a1, float4 t) {
-  const cf t0 = {t.x * a0.x - t.y * a1.x, t.x * a0.y - t.y * a1.y};
-  const cf t1 = {t.y * a0.x + t.x * a1.x, t.y * a0.y + t.x * a1.y};
-  a0 = cmul(t0, cf{t.z, -t.w});
-  a1 = cmul(t1, cf{t.z, t.w});
-}
-
-// adjoint step: given psi, lambda AFTER the gate, accumulate d(theta), d(phi) and undo the gate
-__device__ __forceinline__ void gate_adj(cf& p0, cf& p1, cf& l0, cf& l1, float4 t, float& dth, float& dph) {
-  dph += (l0.x * p0.y - l0.y * p0.x) - (l1.x * p1.y - l1.y * p1.x);   // Im <lam| Z |psi>
-  p0 = cmul(p0, cf{t.z, t.w});
-  l0 = cmul(l0, cf{t.z, t.w});
-  p1 = cmul(p1, cf{t.z, -t.w});
-  l1 = cmul(l1, cf{t.z, -t.w});
-  dth += -(l0.x * p1.x + l0.y * p1.y) + (l1.x * p0.x + l1.y * p0.y); // Im <lam| Y |psi>
-  const cf q0 = p0, q1 = p1, m0 = l0, m1 = l1;
-  p0 = {t.x * q0.x + t.y * q1.x, t.x * q0.y + t.y * q1.y};
-  p1 = {t.x * q1.x - t.y * q0.x, t.x * q1.y - t.y * q0.y};
-  l0 = {t.x * m0.x + t.y * m1.x, t.x * m0.y + t.y * m1.y};
-  l1 = {t.x * m1.x - t.y * m0.x, t.x * m1.y - t.y * m0.y};
-}
 
 // Block-reduce NV per-thread values; dst[off + i] += sum_i (thread i < NV).  red: NW*NV floats.
 template <int NV>

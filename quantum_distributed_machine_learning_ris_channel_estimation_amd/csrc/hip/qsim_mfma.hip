@@ -32,61 +32,22 @@
 // tests/test_qsc_gpu.py::test_qsc_circuit_forward_on_mfma_matches_register_kernel).
 #include <cstdlib>
 
-#include "common.h"
+#include "qsim_mfma_dev.h"
 
 namespace qd {
 namespace qmfma {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 h8;
-typedef __attribute__((ext_vector_type(4))) float f4;
+using namespace qd::qmdev;
+using qd::cf;
+using qd::cmul;
+using qd::hash_normal;
+using qd::ring_fwd_scan;   // (the ring in closed form: this kernel was tuned with it)
+using qd::ring_inv_scan;
 
 constexpr int N = 8;
 constexpr int D = 256;
-constexpr float LO_SCALE = 2048.f, LO_INV = 1.f / 2048.f;
 // operand image of one (group, layer): [op][hl][lane][8] halves; op 0/1 = A_lo blocks for Yr / Yi
 // (B operands of product 1), op 2/3 = A_hi blocks for Zr / Zi (A operands of product 2)
 constexpr int OP_HALVES = 4 * 2 * 64 * 8;
-
-struct cf {
-  float x, y;
-};
-__device__ __forceinline__ cf cmul(cf a, cf b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-
-// R = RZ(phi) RY(theta): [[c e^-ip, -s e^-ip], [s e^ip, c e^ip]] (p = phi / 2), gate_fwd's matrix
-__device__ __forceinline__ cf rot(float c, float s, float cp, float sp, int a, int b) {
-  const float m = (a == b) ? c : (a == 0 ? -s : s);
-  return a == 0 ? cf{m * cp, -m * sp} : cf{m * cp, m * sp};
-}
-// Kronecker product of 4 rotations (qubits q0..q0+3): entry [a][b] (4-bit row / column)
-__device__ __forceinline__ cf kron4(const float4* tr, int q0, int a, int b) {
-  cf v = {1.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float4 t = tr[q0 + i];
-    v = cmul(v, rot(t.x, t.y, t.z, t.w, (a >> i) & 1, (b >> i) & 1));
-  }
-  return v;
-}
-
-__device__ __forceinline__ void split(float v, _Float16& hi, _Float16& lo) {
-  hi = (_Float16)v;
-  lo = (_Float16)((v - (float)hi) * LO_SCALE);
-}
-
-// QuantumNAT noise draw of qsc.hip's qnoise_kernel, element i of the (G, L, N, 2) noisy-weight tensor (the same
-// counter-based hash: the fused prep below writes bit-identical noisy weights)
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z += 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ float hash_normal(unsigned long long seed, unsigned long long ctr, unsigned int i) {
-  const unsigned long long h = mix64(seed ^ mix64(ctr * 0x100000001b3ull + i));
-  const float u1 = ((h >> 40) + 1u) * (1.0f / 16777217.0f);          // (0, 1]
-  const float u2 = ((h >> 16) & 0xffffffu) * (1.0f / 16777216.0f);   // [0, 1)
-  return sqrtf(-2.f * __logf(u1)) * __cosf(6.283185307179586f * u2);
-}
 
 struct Noise {
   const float* w;                 // (L, N, 2) master weights, shared by the G groups
@@ -158,21 +119,6 @@ __global__ void __launch_bounds__(64) prep_kernel(const float* __restrict__ w, _
   }
 }
 
-__device__ __forceinline__ f4 mfma(h8 a, h8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-
-// CNOT ring f (closed form, see qsim_stream.hip) and inverse
-__device__ __forceinline__ int ring_fwd(int k) {
-  int p = k ^ (k << 1);
-  p ^= p << 2;
-  p ^= p << 4;
-  p &= D - 1;
-  return (p & ~1) | ((k ^ (p >> (N - 1))) & 1);
-}
-__device__ __forceinline__ int ring_inv(int j) {
-  const int j2 = j ^ ((j >> (N - 1)) & 1);
-  return j2 ^ ((j2 << 1) & (D - 1));
-}
-
 // x (B, 8) angles, w (G, L, 8, 2) weights (group of sample s = s / wgroup; wgroup 0: one group),
 // ops from prep_kernel; E (B, 8); psave (nullable) psi_final as qsim.hip stores it.
 // Block: 4 waves; each wave runs SPW samples of one group side by side (independent MFMA chains for
@@ -235,7 +181,7 @@ __global__ void __launch_bounds__(256) fwd_kernel(const float* __restrict__ x, c
   h8 xh[SPW], xl[SPW];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const int k = ring_inv((row << 4) | (8 * (gq & 1) + j));
+    const int k = ring_inv_scan<N>((row << 4) | (8 * (gq & 1) + j));
 #pragma unroll
     for (int i = 0; i < SPW; ++i) {
       const cf a = cmul(pt[wv][i][k & 15], pt[wv][i][16 + (k >> 4)]);
@@ -289,7 +235,7 @@ __global__ void __launch_bounds__(256) fwd_kernel(const float* __restrict__ x, c
       for (int i = 0; i < SPW; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int j = ring_fwd(((4 * gq + r) << 4) | row);
+          const int j = ring_fwd_scan<N>(((4 * gq + r) << 4) | row);
           st[wv][i][0][j] = zr[i][r];
           st[wv][i][1][j] = zi[i][r];
         }
@@ -320,7 +266,7 @@ __global__ void __launch_bounds__(256) fwd_kernel(const float* __restrict__ x, c
     for (int q = 0; q < N; ++q) part[q] = 0.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int j = ring_fwd(((4 * gq + r) << 4) | row);
+      const int j = ring_fwd_scan<N>(((4 * gq + r) << 4) | row);
       const float p = zr[i][r] * zr[i][r] + zi[i][r] * zi[i][r];
 #pragma unroll
       for (int q = 0; q < N; ++q) part[q] += ((j >> q) & 1) ? -p : p;

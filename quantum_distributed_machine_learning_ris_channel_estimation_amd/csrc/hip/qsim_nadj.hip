@@ -19,7 +19,7 @@
 // g'_j = gE_j c_j s_j(tau) / T.  A pass builds psi with the frames in the ring gathers (qsim_shots_dev.h, FRAMED),
 // forms lambda, then per layer in reverse: undoes frame and ring together (one index map and one sign, the same for
 // psi and lambda, so a Pauli's overall sign cancels), undoes RZ then RY on every wire of psi and lambda, and takes
-// dphi = Im<lambda|Z|psi>, dtheta = Im<lambda|Y|psi> from the pair sums (qsim_big.hip's gate_adj).
+// dphi = Im<lambda|Z|psi>, dtheta = Im<lambda|Y|psi> from the pair sums (qsim_gates.h gate_adj).
 //
 // Determinism: no float atomics.  A workgroup adds its passes' gradients into its own row in pass order, each address
 // by one fixed thread.  n >= 10 splits a sample's trajectories over 2, 4 or 8 workgroups as qsim_noise.hip does
@@ -43,6 +43,8 @@ namespace qnadj {
 using namespace qd::qshots;
 using namespace qd::qnoise;
 using qd::qpshift::group_bits;
+using qd::gate_adj;
+using qd::ring_fwd;
 
 // LDS carve (bytes): trig (<= 12 float4) | wave partials of the reductions (NW x 2 n floats) | g' (n floats) |
 // <Z_j> of the pass (n floats) | psi | lambda | traj words (T)
@@ -55,47 +57,12 @@ static_assert(NW * 2 * kMaxQubits * sizeof(float) <= O_GW - O_RED, "the reductio
 static_assert(lds_bytes<11>(kMaxTraj) <= (size_t)kLdsBudget, "a quarter of a CU's LDS up to n = 11");
 static_assert(lds_bytes<12>(kMaxTraj) <= 80 * 1024, "two workgroups per CU at n = 12");
 
-// The ring's index map f (ring_inv's inverse): CNOT(q, q+1) for q = 0 .. N-2, then CNOT(N-1, 0).
-template <int N>
-__device__ __forceinline__ int ring_fwd(int k) {
-#pragma unroll
-  for (int i = 0; i <= N - 2; ++i) k ^= ((k >> i) & 1) << (i + 1);
-  k ^= (k >> (N - 1)) & 1;
-  return k;
-}
-
-// Adjoint step of RZ(phi) RY(theta) on a pair (qsim_big.hip's gate_adj): given psi and lambda AFTER the gate, add
-// dphi = Im<lam|Z|psi>, undo RZ, add dtheta = Im<lam|Y|psi>, undo RY.
-__device__ __forceinline__ void gate_adj(cf& p0, cf& p1, cf& l0, cf& l1, float4 t, float& dth, float& dph) {
-  dph += (l0.x * p0.y - l0.y * p0.x) - (l1.x * p1.y - l1.y * p1.x);
-  p0 = cmul(p0, cf{t.z, t.w});
-  l0 = cmul(l0, cf{t.z, t.w});
-  p1 = cmul(p1, cf{t.z, -t.w});
-  l1 = cmul(l1, cf{t.z, -t.w});
-  dth += -(l0.x * p1.x + l0.y * p1.y) + (l1.x * p0.x + l1.y * p0.y);
-  const cf q0 = p0, q1 = p1, m0 = l0, m1 = l1;
-  p0 = {t.x * q0.x + t.y * q1.x, t.x * q0.y + t.y * q1.y};
-  p1 = {t.x * q1.x - t.y * q0.x, t.x * q1.y - t.y * q0.y};
-  l0 = {t.x * m0.x + t.y * m1.x, t.x * m0.y + t.y * m1.y};
-  l1 = {t.x * m1.x - t.y * m0.x, t.x * m1.y - t.y * m0.y};
-}
-
 // Qubits per LDS round trip of the reverse sweep.  Two: a thread then holds 4 amplitudes of psi and of lambda.  With
 // the forward's three (8 + 8 amplitudes and their gate temporaries) the compiler spilled 680 - 820 bytes per lane at
 // n = 9 .. 11 under the four-waves register cap.
 #ifndef QD_NADJ_RB
 #define QD_NADJ_RB 2
 #endif
-
-// The frame of layer m of trajectory tau (a | b << 16): out of line, as in qsim_onchip.hip (inlined, the site loop's
-// registers add to the sweeps').
-template <int N>
-__device__ __noinline__ uint32_t frame_again(int m, uint32_t tau, Rng g, const uint32_t* __restrict__ thr1,
-                                             const uint32_t* __restrict__ thr2) {
-  int fa, fb;
-  layer_frame<N>(m, tau, g, thr1, thr2, fa, fb);
-  return (uint32_t)fa | ((uint32_t)fb << 16);
-}
 
 __device__ __forceinline__ float ro_scale(const uint32_t* thr_ro, int j) {
   return 1.f - (float)(thr_ro[2 * j] + thr_ro[2 * j + 1]) * (1.f / 65536.f);
@@ -375,15 +342,6 @@ __global__ void nadj_finalize_kernel(const float* __restrict__ work, float* __re
     Ebar[(size_t)b * n + (c - P)] = ebar_of(s, thr_ro, c - P, T);
 }
 
-// The chunks per sample: qsim_noise.hip's rule (n >= 10: the most of 8, 4, 2 that divide T and leave a chunk at
-// least 4 trajectories), for the same reason -- a sample's rebuild count varies and few long workgroups drain badly.
-static int choose_split(int T, int n) {
-  if (n < 10) return 1;
-  for (int s = 8; s > 1; s >>= 1)
-    if (T % s == 0 && T / s >= 4) return s;
-  return 1;
-}
-
 template <int N>
 static int launch(const float* x, const float* w, const float* gE, float* G, float* Ebar, int* frames_out, float* work,
                   const uint32_t* thr1, const uint32_t* thr2, const uint32_t* thr_ro, int B, int L, int wgroup, int T,
@@ -408,7 +366,7 @@ static int launch(const float* x, const float* w, const float* gE, float* G, flo
 // The chunks per sample qd_qsim_noisy_adjoint launches for T trajectories of n qubits (0: T out of range).  More
 // than one needs a `work` buffer of chunks x B x (2 n L + n) floats.
 QD_API int qd_qsim_nadj_split(int T, int n) {
-  return T >= 1 && T <= qd::qnoise::kMaxTraj ? qd::qnadj::choose_split(T, n) : 0;
+  return T >= 1 && T <= qd::qnoise::kMaxTraj ? qd::qnoise::choose_split(T, n) : 0;
 }
 
 // G (B, 2 n L) fp32; Ebar (nullable; B, n) fp32; frames_out (nullable; B, T, L, 2) int32: every layer's (a, b).
@@ -420,13 +378,9 @@ QD_API int qd_qsim_noisy_adjoint(const float* x, const float* w, const float* gE
                                  int B, int n, int L, int wgroup, int T, unsigned long long seed,
                                  unsigned long long ctr0, const void* counter, void* stream) {
   using namespace qd::qnoise;
-  if (n < 2 || n > kMaxQubits || B < 1 || L < 1) return (int)hipErrorInvalidValue;
-  if (2ll * n * L > kMaxSites) return (int)hipErrorInvalidValue;
-  if (T < 1 || T > kMaxTraj) return (int)hipErrorInvalidValue;
-  if (wgroup > 0 && B % wgroup != 0) return (int)hipErrorInvalidValue;
+  if (!noisy_args_ok(n, B, L, wgroup, T, thr1, thr2, thr_ro)) return (int)hipErrorInvalidValue;
   if (x == nullptr || w == nullptr || gE == nullptr || G == nullptr) return (int)hipErrorInvalidValue;
-  if (thr1 == nullptr || thr2 == nullptr || thr_ro == nullptr) return (int)hipErrorInvalidValue;
-  const int nsplit = qd::qnadj::choose_split(T, n);
+  const int nsplit = qd::qnoise::choose_split(T, n);
   if (nsplit > 1 && work == nullptr) return (int)hipErrorInvalidValue;
   return dispatch_qubits(n, [&](auto N) {
     return qd::qnadj::launch<N>(x, w, gE, G, Ebar, frames_out, work, (const uint32_t*)thr1, (const uint32_t*)thr2,

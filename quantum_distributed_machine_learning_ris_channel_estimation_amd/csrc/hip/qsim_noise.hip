@@ -183,9 +183,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4)))
   // ---- counts of the four waves -> E / counts
   __syncthreads();
   if (threadIdx.x < N) {
-    int c1 = 0;
-#pragma unroll
-    for (int k = 0; k < NW; ++k) c1 += (int)wcnt[k * N + threadIdx.x];
+    const int c1 = fold_counts<N>(wcnt);
     if (acc_out != nullptr) {   // split grid: the chunks' counts meet here
       if (c1 != 0) atomicAdd(acc_out + (size_t)b * N + threadIdx.x, c1);
     } else {
@@ -205,18 +203,6 @@ __global__ void noisy_finalize_kernel(float* E, int* __restrict__ counts, int to
 }
 
 static int g_force_split = 0;   // 0: choose; else the number of chunks to launch (tests, timing)
-
-// The chunks per sample.  n >= 10, where the kernel's registers allow four workgroups per CU and a workgroup lives
-// long: the most of 8, 4, 2 that divide T and leave a chunk at least 4 trajectories (measured at B = 2304, n = 12,
-// T = 16 at 1e-3 / 1e-2 gate error: 747 us against 860 us with one workgroup per sample).  Below that one workgroup
-// per sample: at n = 8, T = 64 the split gained nothing (342 us against 346 us) and its two extra launches cost
-// 3.5 us at zero thresholds (profiles/noise_timing.txt).
-static int choose_split(int T, int n) {
-  if (n < 10) return 1;
-  for (int s = 8; s > 1; s >>= 1)
-    if (T % s == 0 && T / s >= 4) return s;
-  return 1;
-}
 
 template <int N>
 static int launch_noisy(const float* x, const float* w, float* E, int* counts, float* probs_out, int* frames_out,
@@ -262,12 +248,8 @@ QD_API int qd_qsim_noisy_shots_fwd(const float* x, const float* w, float* E, int
                                    int* frames_out, const void* thr1, const void* thr2, const void* thr_ro, int B,
                                    int n, int L, int wgroup, int shots, int T, unsigned long long seed,
                                    unsigned long long ctr0, const void* counter, void* stream) {
-  if (n < 2 || n > kMaxQubits || shots < 1 || shots > kMaxShots || B < 1 || L < 1) return (int)hipErrorInvalidValue;
-  if (2 * n * L > kMaxSites) return (int)hipErrorInvalidValue;
-  if (T < 1 || T > kMaxTraj || shots % T != 0) return (int)hipErrorInvalidValue;
-  if (T > 1 && (shots / T) % 4 != 0) return (int)hipErrorInvalidValue;
-  if (wgroup > 0 && B % wgroup != 0) return (int)hipErrorInvalidValue;
-  if (thr1 == nullptr || thr2 == nullptr || thr_ro == nullptr) return (int)hipErrorInvalidValue;
+  if (!noisy_args_ok(n, B, L, wgroup, T, thr1, thr2, thr_ro) || !noisy_shots_ok(shots, T))
+    return (int)hipErrorInvalidValue;
   const int nsplit = g_force_split > 0 ? g_force_split : choose_split(T, n);
   if (T % nsplit != 0) return (int)hipErrorInvalidValue;
   return dispatch_qubits(n, [&](auto N) {

@@ -1,6 +1,7 @@
-// Device functions of the noisy finite-shot kernels (qsim_noise.hip, qsim_onchip.hip): the Pauli frame of a layer of a
-// trajectory, the framed draw of a Philox block's four shots with readout flips, and the state -> CDF step.  The
-// contract they implement is stated at the top of qsim_noise.hip.
+// Device functions of the noisy kernels (qsim_noise.hip, qsim_onchip.hip, qsim_nadj.hip): the Pauli frame of a layer of
+// a trajectory, the framed draw of a Philox block's four shots with
+// readout flips, and the state -> CDF step; and the host side the three entry points share (argument checks, chunks
+// per sample).  The contract they implement is stated at the top of qsim_noise.hip.
 #pragma once
 #include "qsim_shots_dev.h"
 
@@ -63,6 +64,16 @@ __device__ __forceinline__ void layer_frame(int l, uint32_t tau, const Rng& g, c
   fb = (int)z;
 }
 
+// The same frame (a | b << 16), out of line: for a kernel that draws a frame again inside its state builds (inlined at
+// every use, the site loop's registers add to the sweeps': qsim_onchip.hip went to scratch from n = 9 up).
+template <int N>
+__device__ __noinline__ uint32_t frame_again(int m, uint32_t tau, Rng g, const uint32_t* __restrict__ thr1,
+                                             const uint32_t* __restrict__ thr2) {
+  int fa, fb;
+  layer_frame<N>(m, tau, g, thr1, thr2, fa, fb);
+  return (uint32_t)fa | ((uint32_t)fb << 16);
+}
+
 // The four shots of Philox block j (shots 4 j .. 4 j + 3) of an `active` lane: outcome from the CDF, the frame's X
 // mask, readout flips, then the wave's bit counts into acc.  Every lane of the wave calls it.
 template <int N>
@@ -112,6 +123,13 @@ __device__ __forceinline__ void flush_counts(uint32_t* wcnt, uint32_t (&acc)[N])
 #pragma unroll
   for (int i = 0; i < N; ++i) acc[i] = 0;
 }
+// Thread i < N: bit i's count, the four waves' rows added to c1 (after a barrier behind the last flush).
+template <int N>
+__device__ __forceinline__ int fold_counts(const uint32_t* wcnt, int c1 = 0) {
+#pragma unroll
+  for (int k = 0; k < NW; ++k) c1 += (int)wcnt[k * N + threadIdx.x];
+  return c1;
+}
 
 // The state in A -> fp32 probabilities (to probs when non-null) -> quantised words over the state -> scanned CDF.
 template <int N>
@@ -136,6 +154,34 @@ __device__ __forceinline__ uint32_t state_to_cdf(cf* A, uint32_t* wtot, float* _
     if (k < D) cdf[cdf_at(k)] = q[i];
   }
   return cdf_scan<N>(cdf, wtot);
+}
+
+// ---- host side of the entry points
+// What every noisy entry point requires of its arguments (else hipErrorInvalidValue).
+static inline bool noisy_args_ok(int n, int B, int L, int wgroup, int T, const void* thr1, const void* thr2,
+                                 const void* thr_ro) {
+  if (n < 2 || n > kMaxQubits || B < 1 || L < 1 || 2ll * n * L > kMaxSites) return false;
+  if (T < 1 || T > kMaxTraj) return false;
+  if (wgroup > 0 && B % wgroup != 0) return false;
+  return thr1 != nullptr && thr2 != nullptr && thr_ro != nullptr;
+}
+// ... and of its shots (T in range): equal shares for the trajectories, whole Philox blocks when there are several.
+static inline bool noisy_shots_ok(int shots, int T) {
+  if (shots < 1 || shots > kMaxShots || shots % T != 0) return false;
+  return T == 1 || (shots / T) % 4 == 0;
+}
+
+// The chunks per sample of the kernels that split a sample's trajectories over workgroups.  n >= 10, where the
+// registers allow several workgroups per CU and a workgroup lives long (a sample's rebuild count varies, and few long
+// workgroups drain badly): the most of 8, 4, 2 that divide T and leave a chunk at least 4 trajectories (measured on
+// qsim_noise.hip at B = 2304, n = 12, T = 16 at 1e-3 / 1e-2 gate error: 747 us against 860 us with one workgroup per
+// sample).  Below that one workgroup per sample: at n = 8, T = 64 the split gained nothing (342 us against 346 us) and
+// its two extra launches cost 3.5 us at zero thresholds (profiles/noise_timing.txt).
+static inline int choose_split(int T, int n) {
+  if (n < 10) return 1;
+  for (int s = 8; s > 1; s >>= 1)
+    if (T % s == 0 && T / s >= 4) return s;
+  return 1;
 }
 
 }  // namespace qnoise

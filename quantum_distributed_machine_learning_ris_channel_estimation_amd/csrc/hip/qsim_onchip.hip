@@ -47,16 +47,6 @@ constexpr size_t lds_bytes(int T) {
 static_assert(lds_bytes<12>(kMaxTraj) <= (size_t)kLdsBudget, "a quarter of a CU's LDS at n = 12");
 static_assert(lds_bytes<11>(kMaxTraj) <= (size_t)kLdsBudget, "a quarter of a CU's LDS at n = 11");
 
-// The frame of layer m of trajectory tau (a | b << 16), drawn again: out of line, for the launches whose frames do
-// not fit the LDS budget (inlined at every use, the site loop's registers went to scratch from n = 9 up).
-template <int N>
-__device__ __noinline__ uint32_t frame_again(int m, uint32_t tau, Rng g, const uint32_t* __restrict__ thr1,
-                                             const uint32_t* __restrict__ thr2) {
-  int fa, fb;
-  layer_frame<N>(m, tau, g, thr1, thr2, fa, fb);
-  return (uint32_t)fa | ((uint32_t)fb << 16);
-}
-
 // (waves_per_eu: at n = 12 the kept state's 64 registers must leave three workgroups per CU, 168 VGPRs.  The cap
 // costs 46 spilled dwords; uncapped, 198 VGPRs and two workgroups per CU measured 2027 against 1581 us at zero
 // thresholds and 13595 against 10350 us at the noise point, B = 256, L = 3, 1024 shots, T = 16:
@@ -289,9 +279,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(N >= 12
   auto finish = [&](int s, const uint32_t* parked) {
     __syncthreads();
     if (threadIdx.x < N) {
-      int c1 = parked != nullptr ? (int)parked[threadIdx.x] : 0;
-#pragma unroll
-      for (int k = 0; k < NW; ++k) c1 += (int)wcnt[k * N + threadIdx.x];
+      const int c1 = fold_counts<N>(wcnt, parked != nullptr ? (int)parked[threadIdx.x] : 0);
       const float e = shots_mean(c1, shots);
       epm[s * N + threadIdx.x] = e;
       if (Epm != nullptr) Epm[slot * N + threadIdx.x] = e;
@@ -352,12 +340,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(N >= 12
       store_plain_probs();
       serve_plain(tot, g);
       __syncthreads();
-      if (threadIdx.x < N) {
-        uint32_t c1 = 0;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) c1 += wcnt[k * N + threadIdx.x];
-        park[ci * N + threadIdx.x] = c1;
-      }
+      if (threadIdx.x < N) park[ci * N + threadIdx.x] = (uint32_t)fold_counts<N>(wcnt);
       __syncthreads();
     }
   }
@@ -416,14 +399,10 @@ QD_API int qd_qsim_noisy_pshift(const float* x, const float* w, const float* gE,
                                 const void* thr_ro, int B, int n, int L, int wgroup, int need_dx, int shots, int T,
                                 unsigned long long seed, unsigned long long ctr0, const void* counter, void* stream) {
   using namespace qd::qnoise;
-  if (n < 2 || n > kMaxQubits || B < 1 || L < 1 || shots < 1 || shots > kMaxShots) return (int)hipErrorInvalidValue;
-  if (2ll * n * L > kMaxSites) return (int)hipErrorInvalidValue;
+  if (!noisy_args_ok(n, B, L, wgroup, T, thr1, thr2, thr_ro) || !noisy_shots_ok(shots, T))
+    return (int)hipErrorInvalidValue;
   if (4ll * n * L + 1 >= (1ll << 16)) return (int)hipErrorInvalidValue;   // stream ids 0 .. 2 P fit 16 bits
-  if (T < 1 || T > kMaxTraj || shots % T != 0) return (int)hipErrorInvalidValue;
-  if (T > 1 && (shots / T) % 4 != 0) return (int)hipErrorInvalidValue;
   if ((long long)B * L * n > 0x7fffffffll) return (int)hipErrorInvalidValue;
-  if (wgroup > 0 && B % wgroup != 0) return (int)hipErrorInvalidValue;
-  if (thr1 == nullptr || thr2 == nullptr || thr_ro == nullptr) return (int)hipErrorInvalidValue;
   return dispatch_qubits(n, [&](auto N) {
     return qd::qonchip::launch<N>(x, w, gE, G, Epm, probs, frames_out, mask, (const uint32_t*)thr1,
                                   (const uint32_t*)thr2, (const uint32_t*)thr_ro, B, L, wgroup, need_dx, shots, T, seed,

@@ -3,15 +3,16 @@
 // kernels), the CDF scan,
 // Philox4x32-10 and the outcome search.  The sampling contract they implement is stated at the top of qsim_shots.hip.
 #pragma once
-#include "common.h"
+#include "qsim_gates.h"
 
 namespace qd {
 namespace qshots {
-
-struct cf {
-  float x, y;
-};
-__device__ __forceinline__ cf cmul(cf a, cf b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+using qd::cf;
+using qd::cmul;
+using qd::frame_sign;
+using qd::gate_fwd;
+using qd::layer_trig;
+using qd::ring_inv;
 
 constexpr int NT = 256;
 constexpr int NW = NT / 64;
@@ -53,38 +54,6 @@ template <int N>
 constexpr size_t smem_bytes(bool state) {
   static_assert(cdf_bytes<N>() <= (int)sizeof(cf) * (1 << N), "the CDF fits over the state");
   return O_DATA + (state ? sizeof(cf) * (1 << N) : cdf_bytes<N>());
-}
-
-template <int N>
-__device__ __forceinline__ int ring_inv(int k) {
-  k ^= (k >> (N - 1)) & 1;
-#pragma unroll
-  for (int i = N - 2; i >= 0; --i) k ^= ((k >> i) & 1) << (i + 1);
-  return k;
-}
-
-// (cos, sin) of theta/2 and (cos, sin) of phi/2 of one layer's qubits, into LDS
-__device__ __forceinline__ void layer_trig(float4* trig, const float* wl, const float* xs, int n) {
-  if (threadIdx.x < n) {
-    const int q = threadIdx.x;
-    float s, c, sp, cp;
-    __sincosf(0.5f * (wl[2 * q] + (xs ? xs[q] : 0.f)), &s, &c);
-    __sincosf(0.5f * wl[2 * q + 1], &sp, &cp);
-    trig[q] = make_float4(c, s, cp, sp);
-  }
-}
-
-// RZ(phi) RY(theta) on the pair (a0: bit 0, a1: bit 1)
-__device__ __forceinline__ void gate_fwd(cf& a0, cf& a1, float4 t) {
-  const cf t0 = {t.x * a0.x - t.y * a1.x, t.x * a0.y - t.y * a1.y};
-  const cf t1 = {t.y * a0.x + t.x * a1.x, t.y * a0.y + t.x * a1.y};
-  a0 = cmul(t0, cf{t.z, -t.w});
-  a1 = cmul(t1, cf{t.z, t.w});
-}
-
-// Sign of a Pauli frame's Z mask fb on basis state js: -a when popc(fb & js) is odd.
-__device__ __forceinline__ cf frame_sign(cf a, int fb, int js) {
-  return (__popc(fb & js) & 1) ? cf{-a.x, -a.y} : a;
 }
 
 // Embedding + layer 0 + ring from the layer's trig: the product state gathered through f^-1, into A (LDS).

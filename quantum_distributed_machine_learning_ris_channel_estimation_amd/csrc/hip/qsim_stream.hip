@@ -35,7 +35,7 @@
 // 21, with psi un-applied and re-stored in every backward pass).
 #include <cstdlib>
 
-#include "common.h"
+#include "qsim_gates.h"
 #include "qsim_shots_dev.h"   // prob_of, quantise: the finite-shot contract's fp32 probability and its 2^30 word
 
 #ifndef QD_STREAM_SWEEP
@@ -56,11 +56,13 @@
 
 namespace qd {
 namespace qstream {
-
-struct cf {
-  float x, y;
-};
-__device__ __forceinline__ cf cmul(cf a, cf b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+using qd::cf;
+using qd::cmul;
+using qd::gate_adj;
+using qd::gate_fwd;
+using qd::ins_bits;
+using qd::ring_fwd_scan;   // (the ring in closed form: the streamed passes were tuned with it)
+using qd::ring_inv_scan;
 
 constexpr int NT = 256;
 constexpr int NWV = NT / 64;
@@ -80,27 +82,6 @@ struct SG {
   static_assert(N >= 13 && N <= 16, "streamed simulator: 13..16 qubits");
 };
 
-// The CNOT ring f and its inverse in closed form: bit j >= 1 of f(k) is the prefix parity of bits
-// 0..j (a log-step XOR scan), bit 0 is k_0 ^ parity(all); f^-1(j): restore bit 0 (= j_0 ^ j_{n-1}),
-// then k_i = j_i ^ j_{i-1}.
-template <int N>
-__device__ __forceinline__ int ring_fwd(int k) {
-  int p = k ^ (k << 1);
-  p ^= p << 2;
-  p ^= p << 4;
-  p ^= p << 8;
-  p &= (1 << N) - 1;
-  return (p & ~1) | ((k ^ (p >> (N - 1))) & 1);
-}
-template <int N>
-__device__ __forceinline__ int ring_inv(int j) {
-  const int j2 = j ^ ((j >> (N - 1)) & 1);
-  return j2 ^ ((j2 << 1) & ((1 << N) - 1));
-}
-template <int P, int NB>
-__device__ __forceinline__ int ins_bits(int t) {
-  return ((t >> P) << (P + NB)) | (t & ((1 << P) - 1));
-}
 // pass-A brick element e -> state index (brick = bits 8..11)
 __device__ __forceinline__ int brick_k(int e, int br) { return (e & 255) | (br << 8) | ((e >> 8) << 12); }
 // pass-A brick bit -> qubit
@@ -135,13 +116,6 @@ __device__ __forceinline__ void product_tables(const float4* trig0, cf* PL, cf* 
   }
 }
 
-// RZ(phi) RY(theta) on the pair (a0: bit 0, a1: bit 1); t = (cos th/2, sin th/2, cos ph/2, sin ph/2)
-__device__ __forceinline__ void gate_fwd(cf& a0, cf& a1, float4 t) {
-  const cf t0 = {t.x * a0.x - t.y * a1.x, t.x * a0.y - t.y * a1.y};
-  const cf t1 = {t.y * a0.x + t.x * a1.x, t.y * a0.y + t.x * a1.y};
-  a0 = cmul(t0, cf{t.z, -t.w});
-  a1 = cmul(t1, cf{t.z, t.w});
-}
 // RY(theta) alone on the pair (the forward's RZ phases applied afterwards, one per amplitude: QD_STREAM_F2)
 __device__ __forceinline__ void gate_ry(cf& a0, cf& a1, float4 t) {
   const cf t0 = {t.x * a0.x - t.y * a1.x, t.x * a0.y - t.y * a1.y};
@@ -149,22 +123,7 @@ __device__ __forceinline__ void gate_ry(cf& a0, cf& a1, float4 t) {
   a0 = t0;
   a1 = t1;
 }
-// adjoint step on psi / lambda AFTER the gate: accumulate d(theta), d(phi), undo the gate on both
-__device__ __forceinline__ void gate_adj(cf& p0, cf& p1, cf& l0, cf& l1, float4 t, float& dth, float& dph) {
-  dph += (l0.x * p0.y - l0.y * p0.x) - (l1.x * p1.y - l1.y * p1.x);
-  p0 = cmul(p0, cf{t.z, t.w});
-  l0 = cmul(l0, cf{t.z, t.w});
-  p1 = cmul(p1, cf{t.z, -t.w});
-  l1 = cmul(l1, cf{t.z, -t.w});
-  dth += -(l0.x * p1.x + l0.y * p1.y) + (l1.x * p0.x + l1.y * p0.y);
-  const cf q0 = p0, q1 = p1, m0 = l0, m1 = l1;
-  p0 = {t.x * q0.x + t.y * q1.x, t.x * q0.y + t.y * q1.y};
-  p1 = {t.x * q1.x - t.y * q0.x, t.x * q1.y - t.y * q0.y};
-  l0 = {t.x * m0.x + t.y * m1.x, t.x * m0.y + t.y * m1.y};
-  l1 = {t.x * m1.x - t.y * m0.x, t.x * m1.y - t.y * m0.y};
-}
-
-// adjoint of the RY half only (the pass's RZ phases already undone, see pass_a_bwd): d(theta) and undo RY
+// gate_adj's RY half only (the pass's RZ phases already undone, see pass_a_bwd): d(theta) and undo RY
 __device__ __forceinline__ void gate_adj_ry(cf& p0, cf& p1, cf& l0, cf& l1, float4 t, float& dth) {
   dth += -(l0.x * p1.x + l0.y * p1.y) + (l1.x * p0.x + l1.y * p0.y);
   const cf q0 = p0, q1 = p1, m0 = l0, m1 = l1;
@@ -630,7 +589,7 @@ __global__ void __launch_bounds__(NT, 2) pass_a_fwd(const float* __restrict__ x,
       __syncthreads();
 #pragma unroll
       for (int j = 0; j < 2 * NPAIR; ++j) {
-        const int k = ring_inv<N>(brick_k(2 * threadIdx.x + 2 * NT * (j >> 1) + (j & 1), br));
+        const int k = ring_inv_scan<N>(brick_k(2 * threadIdx.x + 2 * NT * (j >> 1) + (j & 1), br));
         p[j] = cmul(PL[k & 255], PH[k >> 8]);
       }
     } else {
@@ -670,7 +629,7 @@ __global__ void __launch_bounds__(NT, 2) pass_a_fwd(const float* __restrict__ x,
     product_tables<N, NT>(trig0, PL, PH, 0);
     __syncthreads();
     for (int e = threadIdx.x; e < C::AS; e += NT) {
-      const int k = ring_inv<N>(brick_k(e, br));
+      const int k = ring_inv_scan<N>(brick_k(e, br));
       tp[e] = cmul(PL[k & 255], PH[k >> 8]);
     }
   } else {
@@ -778,9 +737,9 @@ __global__ void __launch_bounds__(NT, 2) pass_b_fwd(const float* __restrict__ x,
     return;
   }
 #pragma unroll
-  for (int h = 0; h < 16; ++h) tp[ring_fwd<N>((t << 12) | (h << 8) | c) & 4095] = a[h];
+  for (int h = 0; h < 16; ++h) tp[ring_fwd_scan<N>((t << 12) | (h << 8) | c) & 4095] = a[h];
   __syncthreads();
-  const int A0 = ring_fwd<N>(t << 12) >> 12, A1 = ring_fwd<N>((t << 12) | 2048) >> 12;
+  const int A0 = ring_fwd_scan<N>(t << 12) >> 12, A1 = ring_fwd_scan<N>((t << 12) | 2048) >> 12;
   cf* dst = out + (size_t)s * C::D;
   float part[N];
 #pragma unroll
@@ -836,9 +795,9 @@ __global__ void __launch_bounds__(NT, 2) pass_b_probs(const float* __restrict__ 
       if (!((h >> b) & 1)) gate_ry(a[h], a[h | (1 << b)], tg);
   }
 #pragma unroll
-  for (int h = 0; h < 16; ++h) tp[ring_fwd<N>((t << 12) | (h << 8) | c) & 4095] = a[h];
+  for (int h = 0; h < 16; ++h) tp[ring_fwd_scan<N>((t << 12) | (h << 8) | c) & 4095] = a[h];
   __syncthreads();
-  const int A0 = ring_fwd<N>(t << 12) >> 12, A1 = ring_fwd<N>((t << 12) | 2048) >> 12;
+  const int A0 = ring_fwd_scan<N>(t << 12) >> 12, A1 = ring_fwd_scan<N>((t << 12) | 2048) >> 12;
   float* dst = probs + (size_t)s * C::D;
   uint32_t rt[2] = {0u, 0u};
 #pragma unroll
@@ -916,7 +875,7 @@ __global__ void __launch_bounds__(NT, QD_STREAM_B4 ? 4 : 2) pass_b_bwd(const flo
     for (int h = 0; h < 16; ++h) p[h] = *reinterpret_cast<const cf*>(src + (unsigned)((h << 8) | c) * 8u);
   }
   if constexpr (QD_STREAM_B4 && !FIRST) {   // lambda at the ring images of this tile's pre-ring amplitudes
-    const int A0 = ring_fwd<N>(t << 12) >> 12, A1 = ring_fwd<N>((t << 12) | 2048) >> 12;
+    const int A0 = ring_fwd_scan<N>(t << 12) >> 12, A1 = ring_fwd_scan<N>((t << 12) | 2048) >> 12;
     const char* ls = reinterpret_cast<const char*>(lin + (size_t)s * C::D);
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
@@ -956,11 +915,11 @@ __global__ void __launch_bounds__(NT, QD_STREAM_B4 ? 4 : 2) pass_b_bwd(const flo
     // states and the store loop before: 1 LDS scatter + 1 gather and 2 barriers now, against 6 sweeps and 4.
     cf m[16];
     if constexpr (!FIRST) {   // lambda (loaded at the top, all 16 in flight) -> pre-ring order in LDS
-      const int A0 = ring_fwd<N>(t << 12) >> 12, A1 = ring_fwd<N>((t << 12) | 2048) >> 12;
+      const int A0 = ring_fwd_scan<N>(t << 12) >> 12, A1 = ring_fwd_scan<N>((t << 12) | 2048) >> 12;
 #pragma unroll
       for (int u = 0; u < 16; ++u) {
         const int i = threadIdx.x + NT * u;
-        tq[ring_inv<N>(i | ((i & 2048 ? A1 : A0) << 12)) & 4095] = lv[u];
+        tq[ring_inv_scan<N>(i | ((i & 2048 ? A1 : A0) << 12)) & 4095] = lv[u];
       }
     }
     __syncthreads();   // (the scatter; FIRST: the observable tables; GEN0: the product tables)
@@ -979,7 +938,7 @@ __global__ void __launch_bounds__(NT, QD_STREAM_B4 ? 4 : 2) pass_b_bwd(const flo
 #pragma unroll
     for (int h = 0; h < 16; ++h) {
       if constexpr (FIRST) {   // lambda = O psi_final, psi_final(ring(k)) = psi(k)
-        const int j = ring_fwd<N>((t << 12) | (h << 8) | c);
+        const int j = ring_fwd_scan<N>((t << 12) | (h << 8) | c);
         const float o = OL[j & 255] + OH[j >> 8];
         m[h] = {p[h].x * o, p[h].y * o};
       } else {
@@ -1064,12 +1023,12 @@ __global__ void __launch_bounds__(NT, QD_STREAM_B4 ? 4 : 2) pass_b_bwd(const flo
     return;
   }
   if constexpr (!FIRST) {   // lambda at the ring images -> pre-ring order in LDS
-    const int A0 = ring_fwd<N>(t << 12) >> 12, A1 = ring_fwd<N>((t << 12) | 2048) >> 12;
+    const int A0 = ring_fwd_scan<N>(t << 12) >> 12, A1 = ring_fwd_scan<N>((t << 12) | 2048) >> 12;
     const cf* ls = lin + (size_t)s * C::D;
 #pragma unroll 4
     for (int i = threadIdx.x; i < 4096; i += NT) {
       const int j = i | ((i & 2048 ? A1 : A0) << 12);
-      tq[ring_inv<N>(j) & 4095] = ls[j];
+      tq[ring_inv_scan<N>(j) & 4095] = ls[j];
     }
   }
   if constexpr (!GEN0) {   // psi = S_l with this layer's rotations 8..11 re-applied (registers)
@@ -1093,7 +1052,7 @@ __global__ void __launch_bounds__(NT, QD_STREAM_B4 ? 4 : 2) pass_b_bwd(const flo
   }
   if constexpr (FIRST) {   // lambda = O psi_final, psi_final(ring(k)) = psi(k)
     for (int i = threadIdx.x; i < 4096; i += NT) {
-      const int j = ring_fwd<N>((t << 12) | i);
+      const int j = ring_fwd_scan<N>((t << 12) | i);
       const float o = OL[j & 255] + OH[j >> 8];
       const cf p = tp[i];
       tq[i] = {p.x * o, p.y * o};
