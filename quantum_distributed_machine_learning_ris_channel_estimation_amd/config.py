@@ -161,6 +161,9 @@ class EvalConfig:
     # "soft" (additionally: the experts combined under the classifier's posterior, and the oracle routing by the true
     # scenario -- the nmse_*_soft / nmse_oracle rows)
     routing: str = "hard"
+    # precision of the shared FC at test time: "bf16", or "fp8" -- OCP e4m3 with one power-of-two scale per operand
+    # row (sample, expert) and per output channel (no calibration; the precision the fp8 estimator is trained in)
+    dtype: str = "bf16"
 
     def update_from_dict(self, d: Dict[str, Any]) -> "EvalConfig":
         names = {f.name for f in dataclasses.fields(self)}

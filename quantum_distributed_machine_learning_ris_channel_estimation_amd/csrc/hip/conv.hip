@@ -2680,6 +2680,68 @@ __global__ void __launch_bounds__(256) bn_relu_apply_kernel(const uint16_t* __re
   if (h8) amax_block_store(amax, mx);
 }
 
+// The eval BN + ReLU apply that quantises every FC-operand row on its own (the e4m3 test-time estimator): one
+// workgroup per row r = n E + e (the 32 HW contiguous elements of sample n, expert e), every thread keeps its
+// 32 HW / 256 activations in registers, so z is read once:
+//   h   = bf16(relu(a z + b))                         -- the value bn_relu_apply_kernel stores (h3: nullable copy)
+//   e_r = the smallest integer with 448 2^e_r >= max_row h, clamped to [-32, 32]; 0 for an all-zero row
+//   h8  = e4m3(h 2^-e_r)  (an exact scaling, ONE rounding),  rs[r] = 2^e_r
+// No calibrated per-tensor scale: a row's bytes depend on that row alone.
+__device__ __forceinline__ int e4m3_scale_exponent(float m) {
+  // m = 1.f x 2^x (m >= 0); 448 = 1.75 x 2^8: e = x - 8 when 1.f <= 1.75, else x - 7
+  const uint32_t bits = __float_as_uint(m);
+  if ((bits & 0x7fffffffu) == 0u) return 0;
+  const int x = (int)((bits >> 23) & 0xffu) - 127;
+  const int e = x - ((bits & 0x7fffffu) <= 0x600000u ? 8 : 7);
+  return e < -32 ? -32 : e > 32 ? 32 : e;
+}
+template <int HW>
+__global__ void __launch_bounds__(256) bn_relu_rows_f8_kernel(const uint16_t* __restrict__ z,
+                                                              const float* __restrict__ st, uint8_t* __restrict__ h8,
+                                                              float* __restrict__ rs, uint16_t* __restrict__ h3, int E,
+                                                              int B) {
+  constexpr int NI = CO * HW / (8 * 256);   // 8-value items per thread (2 or 4)
+  __shared__ float wmax[4];
+  const int r = blockIdx.x, n = r / E, e = r % E;
+  const size_t row0 = (size_t)r * (CO * HW);
+  const float* rec = st + ((size_t)(n / B) * (E * CO) + e * CO) * NST;
+  float v[NI][8];
+  float mx = 0.f;
+#pragma unroll
+  for (int k = 0; k < NI; ++k) {
+    const int i8 = (threadIdx.x + 256 * k) * 8;
+    const float* sc = rec + (i8 / HW) * NST;
+    const float a = sc[ST_A], b = sc[ST_B];
+    load8(z + row0 + i8, v[k]);
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[k][j] = relu_nan(a * v[k][j] + b);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] = f32_to_bf16(v[k][2 * j]) | ((uint32_t)f32_to_bf16(v[k][2 * j + 1]) << 16);
+    if (h3 != nullptr) *reinterpret_cast<uint4*>(h3 + row0 + i8) = make_uint4(w[0], w[1], w[2], w[3]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {   // (quantised from the bf16-rounded value)
+      v[k][2 * j] = __uint_as_float(w[j] << 16);
+      v[k][2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
+      mx = fmaxf(mx, fmaxf(v[k][2 * j], v[k][2 * j + 1]));
+    }
+  }
+  mx = wave_max(mx);
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+  const int ex = e4m3_scale_exponent(mx);
+  const float q = __uint_as_float((uint32_t)(127 - ex) << 23);   // 2^-ex
+  if (threadIdx.x == 0) rs[r] = __uint_as_float((uint32_t)(127 + ex) << 23);
+#pragma unroll
+  for (int k = 0; k < NI; ++k) {
+    const int i8 = (threadIdx.x + 256 * k) * 8;
+    const uint32_t p0 = e4m3_pack4(v[k][0] * q, v[k][1] * q, v[k][2] * q, v[k][3] * q);
+    const uint32_t p1 = e4m3_pack4(v[k][4] * q, v[k][5] * q, v[k][6] * q, v[k][7] * q);
+    *reinterpret_cast<uint2*>(h8 + row0 + i8) = make_uint2(p0, p1);
+  }
+}
+
 // Layer-3 BN + ReLU apply with the BN tail folded in: one launch instead of two.
 // Workgroups [0, U*ach*E), (u, chunk, e): build the (u, e) records from the conv's statistics partials
 // (bn_fwd_build, as the conv kernels do for layers 1 / 2; chunk 0 publishes them for the backward), then
@@ -3381,6 +3443,22 @@ QD_API int qd_bn_relu_apply(const uint16_t* z, const float* st, uint16_t* h, int
                        h8, qs, amax);
   else
     return (int)hipErrorInvalidValue;
+  return (int)hipGetLastError();
+}
+
+// The row-quantising eval apply (bn_relu_rows_f8_kernel): z (N, E 32, HW) bf16 and st the published layer-3 records
+// (N / B groups, E 32 channels; qd_bn_stats_finalize_multi builds them) -> h8 (N E, 32 HW) e4m3, rs (N E,) fp32
+// powers of two, and h3 (N E, 32 HW) bf16 when not null.  HW 128 or 256; a null h8 / rs or any other HW is refused
+// before any launch.
+QD_API int qd_bn_relu_rows_f8(const uint16_t* z, const float* st, uint8_t* h8, float* rs, uint16_t* h3, int N, int E,
+                              int B, int HW, void* stream) {
+  if (!z || !st || !h8 || !rs || N < 1 || E < 1 || B < 1 || (HW != 128 && HW != 256) || (long)N * E > (1L << 30))
+    return (int)hipErrorInvalidValue;
+  const dim3 grid(N * E);
+  if (HW == 128)
+    hipLaunchKernelGGL((bn_relu_rows_f8_kernel<128>), grid, dim3(256), 0, (hipStream_t)stream, z, st, h8, rs, h3, E, B);
+  else
+    hipLaunchKernelGGL((bn_relu_rows_f8_kernel<256>), grid, dim3(256), 0, (hipStream_t)stream, z, st, h8, rs, h3, E, B);
   return (int)hipGetLastError();
 }
 

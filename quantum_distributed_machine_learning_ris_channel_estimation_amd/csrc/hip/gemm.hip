@@ -49,6 +49,9 @@
 //   EPI_MIX   the inference forward over ALL experts' rows with the posterior-weighted combination of each
 //             sample's three product rows in the row pass: C[i] bf16 = sum_e p[i, e] acc[3 i + e] (+ bias)
 //             (qd_gemm_fwd_mix: soft test-time routing; the mix is in fp32, after the product)
+//   row / column scales (Args::rsc / csc, the e4m3 test-time forwards qd_gemm_fwd_rows_f8 / qd_gemm_fwd_mix_rows_f8):
+//             every operand row of A and every output column carries its own power-of-two dequantisation scale,
+//             applied to the fp32 accumulators in the row pass of EPI_BF16 (with the routed row's index) and EPI_MIX
 #include <type_traits>
 
 #include "common.h"
@@ -445,6 +448,11 @@ struct Args {
   AdamEpi ad;           // EPI_ADAM
   const float* deq2;    // nullable: with deq, the scales are deq[0] and deq2[0] (two separate scale slots)
   BnRedEpi br;          // EPI_BF16: nullable BN backward reduction (see BnRedEpi)
+  // (e4m3 forward tiles; EPI_BF16: nullable, both or none, deq null; EPI_MIX on e4m3 operands: required) per-row and
+  // per-column dequantisation: rsc[r] for SOURCE row r of P (r = i * pe + pexp[i] when routed), csc[j] for output
+  // column j, exact powers of two
+  const float* rsc;
+  const float* csc;
 };
 
 // EPI_NMSE on a Geo::PFQ tile: the producer waves fetch the tile's label and perfect-channel rows into registers
@@ -1179,6 +1187,23 @@ __global__ void __launch_bounds__(G::NT, 1) gemm_kernel(Args a) {
         return;
       }
     }
+    if constexpr (G::F8 != 0 && G::LA == KC && G::LB == KC && G::BM == 144 && VEC == 2) {
+      // y = bf16(fma(acc, rs[r] cs[j], b[j])): the scales are powers of two, so their product and the scaling are
+      // exact and the fma is the one fp32 rounding before the store
+      if (a.rsc != nullptr) {
+        const float cv0 = a.csc[j0 + c0], cv1 = a.csc[j0 + c0 + 1];
+        for (int row = wave; row < G::BM; row += G::NW) {
+          const int gi = i0 + row;
+          const size_t r = a.pexp ? (size_t)gi * a.pe + a.pexp[gi] : (size_t)gi;
+          const float rv = a.rsc[r];
+          const float2 v = *reinterpret_cast<const float2*>(ct + row * PITCH + c0);
+          *reinterpret_cast<uint32_t*>(C + (size_t)gi * a.ldc + j0 + c0) =
+              (uint32_t)f32_to_bf16(__builtin_fmaf(v.x, rv * cv0, bv[0])) |
+              ((uint32_t)f32_to_bf16(__builtin_fmaf(v.y, rv * cv1, bv[1])) << 16);
+        }
+        return;
+      }
+    }
     for (int row = wave; row < G::BM; row += G::NW) {
       const float* src = ct + row * PITCH + c0;
       uint16_t* dst = C + (size_t)(i0 + row) * a.ldc + j0 + c0;
@@ -1199,14 +1224,29 @@ __global__ void __launch_bounds__(G::NT, 1) gemm_kernel(Args a) {
     // whole samples, as in the training epilogues' 3-expert fast paths): one output row per wave pass,
     // y = fma(p2, acc2, fma(p1, acc1, p0 acc0)) in fp32, then bias and rounding as EPI_BF16.  With a one-hot p the
     // chain returns the selected accumulator unchanged (1 acc + 0 finite is exact), i.e. the routed forward's row.
-    static_assert(G::BM % 3 == 0 && G::KS == 1 && G::F8 == 0, "whole 3-expert samples per tile, bf16 operands");
+    // e4m3 operands (the 144-row tiles, row / column scales): p'_e = p_e rs[3 i + e] (exact), the same chain on the
+    // scaled weights, then y = bf16(fma(m, cs[j], b[j])) -- with a one-hot p the chain returns acc rs exactly and
+    // the store is the routed e4m3 forward's fma(acc, rs cs, b) bit for bit.
+    static_assert(G::BM % 3 == 0 && G::KS == 1 && (G::F8 == 0 || G::BM == 144),
+                  "whole 3-expert samples per tile; e4m3 operands: the 144-row tiles");
     uint16_t* C = reinterpret_cast<uint16_t*>(a.C);
     float bv[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) bv[v] = a.bias ? bf16_to_f32(a.bias[j0 + c0 + v]) : 0.f;
     const float* pw3 = a.mx.p + i0;   // (3 (i0 / 3) = i0)
+    [[maybe_unused]] float cv[VEC];
+    if constexpr (G::F8 != 0) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) cv[v] = a.csc[j0 + c0 + v];
+    }
     for (int s = __builtin_amdgcn_readfirstlane(wave); s < G::BM / 3; s += G::NW) {
-      const float p0 = pw3[3 * s], p1 = pw3[3 * s + 1], p2 = pw3[3 * s + 2];
+      float p0 = pw3[3 * s], p1 = pw3[3 * s + 1], p2 = pw3[3 * s + 2];
+      if constexpr (G::F8 != 0) {
+        const float* rs3 = a.rsc + i0 + 3 * s;
+        p0 *= rs3[0];
+        p1 *= rs3[1];
+        p2 *= rs3[2];
+      }
       const float* src = ct + 3 * s * PITCH + c0;
       uint16_t* dst = C + (size_t)(i0 / 3 + s) * a.ldc + j0 + c0;
       using VT = std::conditional_t<VEC == 4, float4, float2>;
@@ -1215,7 +1255,13 @@ __global__ void __launch_bounds__(G::NT, 1) gemm_kernel(Args a) {
       const float *x0 = &v0.x, *x1 = &v1.x, *x2 = &v2.x;
       float m[VEC];
 #pragma unroll
-      for (int v = 0; v < VEC; ++v) m[v] = __builtin_fmaf(p2, x2[v], __builtin_fmaf(p1, x1[v], p0 * x0[v])) + bv[v];
+      for (int v = 0; v < VEC; ++v) {
+        if constexpr (G::F8 != 0)
+          m[v] = __builtin_fmaf(__builtin_fmaf(p2, x2[v], __builtin_fmaf(p1, x1[v], rounded_product(p0, x0[v]))), cv[v],
+                                bv[v]);
+        else
+          m[v] = __builtin_fmaf(p2, x2[v], __builtin_fmaf(p1, x1[v], p0 * x0[v])) + bv[v];
+      }
       if constexpr (VEC == 4) {
         uint2 w;
         w.x = (uint32_t)f32_to_bf16(m[0]) | ((uint32_t)f32_to_bf16(m[1]) << 16);
@@ -1707,6 +1753,54 @@ QD_API int qd_gemm_fwd_bias_f8(const uint8_t* A8, const uint8_t* W8, const float
   if (cfg == 2) return launch<FwdM8P, EPI_BF16, 4, 8>(a, (hipStream_t)stream);
   if (cfg == 1) return launch<FwdM8, EPI_BF16, 4, 8>(a, (hipStream_t)stream);
   return launch<FwdA8, EPI_BF16, 4, 8>(a, (hipStream_t)stream);
+}
+
+// The e4m3 test-time forwards with per-row and per-column power-of-two scales (no calibration pass, and a sample's
+// estimate does not depend on its neighbours): A8 (rows, K) e4m3 with rs (rows,) fp32 = 2^e_r, the FC operand rows
+// as csrc/hip/conv.hip qd_bn_relu_rows_f8 writes them; W8 (N, K) e4m3 with cs (N,) fp32 = 2^f_j; bias (N,) bf16
+// nullable.  cfg 0: FwdA8 (K % 128 == 0), 1: FwdM8 (MX MFMA, unit block scales, K % 256 == 0), 2: FwdM8P (the same
+// with producer waves).  Anything else than the rules below: hipErrorInvalidValue before any launch, Y untouched.
+static int rows_f8_ok(const void* A8, const void* W8, const float* rs, const float* cs, const void* Y, long rows, int N,
+                      int K, int cfg) {
+  if (!A8 || !W8 || !rs || !cs || !Y || cfg < 0 || cfg > 2) return 0;
+  if (rows < FwdA8::BM || rows > (1L << 30) || rows % FwdA8::BM || N < FwdA8::BN || N % FwdA8::BN) return 0;
+  return K >= (cfg ? 256 : 128) && K % (cfg ? 256 : 128) == 0;
+}
+template <int EPI>
+static int launch_rows_f8(const Args& a, int cfg, void* stream) {
+  if (cfg == 2) return launch<FwdM8P, EPI, 4, 8>(a, (hipStream_t)stream);
+  if (cfg == 1) return launch<FwdM8, EPI, 4, 8>(a, (hipStream_t)stream);
+  return launch<FwdA8, EPI, 4, 8>(a, (hipStream_t)stream);
+}
+// Routed: Y[i, j] (M, N) bf16 = bf16(fma(acc[r_i, j], rs[r_i] cs[j], b[j])), r_i = i E + expert[i] (expert (M,) int64,
+// values < E; null: r_i = i and A8 has M rows).  M % 144 == 0, N % 128 == 0.
+QD_API int qd_gemm_fwd_rows_f8(const uint8_t* A8, const uint8_t* W8, const float* rs, const float* cs,
+                               const uint16_t* bias, uint16_t* Y, int M, int N, int K, int cfg, const long* expert, int E,
+                               void* stream) {
+  if (!rows_f8_ok(A8, W8, rs, cs, Y, M, N, K, cfg) || (expert != nullptr && (E < 1 || E > 64)))
+    return (int)hipErrorInvalidValue;
+  const int K2 = K / 2;   // 2-byte units of an e4m3 row
+  Args a{reinterpret_cast<const uint16_t*>(A8), reinterpret_cast<const uint16_t*>(W8), K2, K2, M, N, K2, Y, N, bias, {},
+         expert, expert ? E : 0, nullptr};
+  a.rsc = rs;
+  a.csc = cs;
+  return launch_rows_f8<EPI_BF16>(a, cfg, stream);
+}
+// Mixed: Y[i, j] (M, N) bf16 = bf16(fma(m, cs[j], b[j])), m = fma(p'_2, acc[3 i + 2, j], fma(p'_1, acc[3 i + 1, j],
+// p'_0 acc[3 i, j])), p'_e = P[i, e] rs[3 i + e]; P (M, 3) fp32.  E == 3, (M E) % 144 == 0, N % 128 == 0.  A one-hot P
+// gives qd_gemm_fwd_rows_f8's routed rows bit for bit.
+QD_API int qd_gemm_fwd_mix_rows_f8(const uint8_t* A8, const uint8_t* W8, const float* rs, const float* cs,
+                                   const uint16_t* bias, const float* P, uint16_t* Y, int M, int N, int K, int E, int cfg,
+                                   void* stream) {
+  if (E != 3 || !P || M < 1 || M > (1 << 28) || !rows_f8_ok(A8, W8, rs, cs, Y, (long)M * E, N, K, cfg))
+    return (int)hipErrorInvalidValue;
+  const int K2 = K / 2;
+  Args a{reinterpret_cast<const uint16_t*>(A8), reinterpret_cast<const uint16_t*>(W8), K2, K2, M * E, N, K2, Y, N, bias, {},
+         nullptr, 0, nullptr};
+  a.mx = MixEpi{P};
+  a.rsc = rs;
+  a.csc = cs;
+  return launch_rows_f8<EPI_MIX>(a, cfg, stream);
 }
 
 // C[I, J] = sP sQ sum_k P8[i, k] Q8[j, k] on the MX-scaled e4m3 MFMA: P8 (I, K), Q8 (J, K) row-major e4m3 (the

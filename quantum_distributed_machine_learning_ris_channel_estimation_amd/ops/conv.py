@@ -158,6 +158,13 @@ class ConvStackHIP:
         # the BN tail (running statistics) and layer 3's BN/ReLU apply as ONE launch (False: two launches, the
         # tail publishing layer 3's records -- 1 launch more on the chain)
         self.apply_tail = True
+        # the e4m3 test-time estimator (train/infer.py, dtype="fp8"): an eval forward ends in the row-quantising apply
+        # (qd_bn_relu_rows_f8) and returns h8r (N E, 32 HW) e4m3, every row scaled by its own power of two rs (N E,);
+        # the bf16 operand is written only into rows_h3 when the owner supplies one (tests)
+        self.rows_f8 = False
+        self.rows_h3 = None
+        self.h8r = self.rs = None
+        self._rows8 = nat.fn(L, "qd_bn_relu_rows_f8", [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p])
         self.spb_a = 8   # (samples per BN-apply workgroup; a group's last workgroup may be partial)
         self._packm = nat.fn(L, "qd_conv_pack_weights_multi", [_i, _p, _p, _p, _p, _i, _p])
         self._packm2 = nat.fn(L, "qd_conv_pack_weights_multi2", [_i, _p, _p, _p, _p, _i, _p, _i, _p])
@@ -241,7 +248,8 @@ class ConvStackHIP:
 
     # --------------------------------------------------------------------- forward
     def forward(self, x1: torch.Tensor, training: bool) -> torch.Tensor:
-        """x1: (N, E*2, H, W) fp32 contiguous.  Returns the FC operand (N*E, 32*H*W) bf16."""
+        """x1: (N, E*2, H, W) fp32 contiguous.  Returns the FC operand (N*E, 32*H*W) bf16 -- with ``rows_f8`` and
+        ``training=False`` the e4m3 one, its row scales in ``self.rs``."""
         m, st = self.m, nat.stream_ptr(x1.device)
         assert x1.shape == (self.N, 2 * self.E, self.H, self.W) and x1.dtype == torch.float32 and x1.is_contiguous()
         self.x1 = x1
@@ -306,6 +314,19 @@ class ConvStackHIP:
         nbt = getattr(m, "_nbt", None) if (training and self.count_batches) else None
         arr = lambda xs: (ctypes.c_void_p * 3)(*[nat.ptr(x) for x in xs])
         f8 = self.m.fp8_scales if self.fp8 else None
+        if self.rows_f8 and not training:
+            if self.h8r is None:
+                self.h8r = torch.empty(self.N * self.E, 32 * self.HW, device=x1.device, dtype=torch.float8_e4m3fn)
+                self.rs = torch.empty(self.N * self.E, device=x1.device)
+            # the BN tail publishes layer 3's records (running statistics), the apply reads them
+            nat.check(self._fin(3, arr(self.stats), arr(m.bn_w), arr(m.bn_b), arr(m.run_mean), arr(m.run_var),
+                                arr(self.st), self.U, self.chunks_f, self.EC, float(self.B * self.HW), m.momentum, m.eps,
+                                0, None, 0, self.U, st), "bn_tail")
+            h3 = self.rows_h3
+            assert h3 is None or (h3.dtype == torch.bfloat16 and h3.shape == self.h3.shape and h3.is_contiguous())
+            nat.check(self._rows8(nat.ptr(self.z[2]), nat.ptr(self.st[2]), nat.ptr(self.h8r), nat.ptr(self.rs),
+                                  _ptr(h3), self.N, self.E, self.B, self.HW, st), "bn_relu_rows_f8")
+            return self.h8r
         if self.apply_tail:
             bnf3 = BnFwd(nat.ptr(self.stats[2]), nat.ptr(m.bn_w[2]), nat.ptr(m.bn_b[2]), nat.ptr(m.run_mean[2]),
                          nat.ptr(m.run_var[2]), nat.ptr(self.st[2]), self.chunks_f, float(self.B * self.HW),

@@ -165,6 +165,61 @@ def gemm_fwd_f8(A8: torch.Tensor, W8: torch.Tensor, deq: torch.Tensor, b: Option
     return Y
 
 
+def _rows_f8_operands(A8, W8, rs, cs, b):
+    K = A8.shape[1]
+    N = W8.shape[0]
+    assert A8.dtype == W8.dtype == torch.float8_e4m3fn and A8.is_contiguous() and W8.is_contiguous()
+    assert W8.shape[1] == K and W8.device == A8.device
+    for s, n in ((rs, A8.shape[0]), (cs, N)):
+        assert s.dtype == torch.float32 and s.is_contiguous() and s.numel() == n and s.device == A8.device
+    assert b is None or (b.dtype == torch.bfloat16 and b.numel() == N and b.is_contiguous())
+    return N, K
+
+
+def gemm_fwd_rows_f8(A8: torch.Tensor, W8: torch.Tensor, rs: torch.Tensor, cs: torch.Tensor,
+                     b: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, cfg: int = 2,
+                     expert: Optional[torch.Tensor] = None, n_experts: int = 0) -> torch.Tensor:
+    """Y[i, j] = bf16(fma(acc[r_i, j], rs[r_i] cs[j], b[j])), acc = A8 W8^T in fp32: the e4m3 test-time forward with
+    one power-of-two scale per operand row (``rs``, one per row of A8) and per output channel (``cs`` (N,))
+    (csrc/hip/gemm.hip qd_gemm_fwd_rows_f8).  ``expert`` ((M,) int64, values < ``n_experts``): r_i =
+    i * n_experts + expert[i], the routed rows as ``gemm_fwd``'s; else r_i = i.  cfg 0: mfma_f32_16x16x32_fp8_fp8
+    (K % 128 == 0); 1: the MX-scaled MFMA with unit block scales (K % 256 == 0); 2: the same with producer waves.
+    M % 144 == 0, N % 128 == 0; anything else raises RuntimeError before any launch."""
+    N, K = _rows_f8_operands(A8, W8, rs, cs, b)
+    M = A8.shape[0]
+    if expert is not None:
+        assert expert.dtype == torch.int64 and expert.is_contiguous() and expert.device == A8.device
+        M = expert.numel()
+        assert A8.shape[0] >= M * n_experts
+    Y = out if out is not None else torch.empty(M, N, device=A8.device, dtype=torch.bfloat16)
+    assert Y.dtype == torch.bfloat16 and Y.shape[0] >= M and Y.shape[1] == N and Y.is_contiguous()
+    f = _gemm_fn("qd_gemm_fwd_rows_f8", [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p])
+    nat.check(f(nat.ptr(A8), nat.ptr(W8), nat.ptr(rs), nat.ptr(cs), nat.ptr(b) if b is not None else None, nat.ptr(Y),
+                M, N, K, cfg, nat.ptr(expert) if expert is not None else None, n_experts,
+                nat.stream_ptr(A8.device)), "gemm_fwd_rows_f8")
+    return Y
+
+
+def gemm_fwd_mix_rows_f8(A8: torch.Tensor, W8: torch.Tensor, rs: torch.Tensor, cs: torch.Tensor,
+                         b: Optional[torch.Tensor], weights: torch.Tensor, out: Optional[torch.Tensor] = None,
+                         cfg: int = 2) -> torch.Tensor:
+    """The e4m3 soft-routed forward (csrc/hip/gemm.hip qd_gemm_fwd_mix_rows_f8): with p'_e = weights[i, e] rs[3 i + e],
+    Y[i, j] = bf16(fma(fma(p'_2, acc[3 i + 2, j], fma(p'_1, acc[3 i + 1, j], p'_0 acc[3 i, j])), cs[j], b[j])).
+    Operands as ``gemm_fwd_rows_f8`` (A8 has M E rows), ``weights`` (M, E) fp32; one-hot weights give the routed
+    call bit for bit.  E == 3, (M E) % 144 == 0, N % 128 == 0, cfg as there; anything else raises RuntimeError."""
+    assert weights.dim() == 2 and weights.dtype == torch.float32 and weights.is_contiguous()
+    assert weights.device == A8.device
+    M, E = weights.shape
+    N, K = _rows_f8_operands(A8, W8, rs, cs, b)
+    assert A8.shape[0] >= M * E
+    Y = out if out is not None else torch.empty(M, N, device=A8.device, dtype=torch.bfloat16)
+    assert Y.dtype == torch.bfloat16 and Y.shape[0] >= M and Y.shape[1] == N and Y.is_contiguous()
+    f = _gemm_fn("qd_gemm_fwd_mix_rows_f8", [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p])
+    nat.check(f(nat.ptr(A8), nat.ptr(W8), nat.ptr(rs), nat.ptr(cs), nat.ptr(b) if b is not None else None,
+                nat.ptr(weights), nat.ptr(Y), M, N, K, E, cfg, nat.stream_ptr(A8.device)), "gemm_fwd_mix_rows_f8")
+    return Y
+
+
 def gemm_nt_f8(P8: torch.Tensor, Q8: torch.Tensor, sP: torch.Tensor, sQ: torch.Tensor, out: Optional[torch.Tensor] = None,
                out_dtype=torch.bfloat16, cfg: int = 1) -> torch.Tensor:
     """C (I, J) = sP sQ P8 Q8^T on the MX-scaled e4m3 MFMA (csrc/hip/gemm.hip qd_gemm_nt_f8): P8 (I, K), Q8 (J, K)

@@ -238,13 +238,17 @@ class HDCEModel:
 
 @torch.no_grad()
 def estimate_routed(convs: Sequence[nn.Module], fc: nn.Module, x: torch.Tensor, expert: torch.Tensor,
-                    chunk: int = 4096) -> torch.Tensor:
+                    chunk: int = 4096, dtype: str = "bf16") -> torch.Tensor:
     """Test-time hierarchical routing (Test.py:166-214): sample i -> Conv_{expert[i]} -> shared CE.
 
     MoE-style top-1 routing: samples are bucketed by expert with ONE stable sort (the
     reference loops over samples in Python), each bucket runs through its expert, and the
-    outputs are scattered back to input order."""
+    outputs are scattered back to input order.
+
+    ``dtype="fp8"``: the shared FC in e4m3 with per-row and per-channel power-of-two scales (the definition below):
+    Y[i, j] = bf16(fma(acc[i, j], rs[i] cs[j], b[j]))."""
     E = len(convs)
+    f8 = _fp8_fc_operands(fc) if _infer_dtype(dtype) == "fp8" else None
     order = torch.argsort(expert, stable=True)
     counts = torch.bincount(expert, minlength=E).tolist()
     xs = x[order]
@@ -254,28 +258,108 @@ def estimate_routed(convs: Sequence[nn.Module], fc: nn.Module, x: torch.Tensor, 
         for s in range(start, start + c, chunk):
             t = min(s + chunk, start + c)
             h = convs[e](xs[s:t].float())
-            out[order[s:t]] = fc(h).float()
+            if f8 is not None:
+                W8, cs, b = f8
+                acc, rs = _fp8_rows_acc(h, W8)
+                out[order[s:t]] = _fma_f32(acc, rs[:, None] * cs[None, :], b).bfloat16().float()
+            else:
+                out[order[s:t]] = fc(h).float()
         start += c
     return out
 
 
 @torch.no_grad()
 def estimate_mixed(convs: Sequence[nn.Module], fc: nn.Module, x: torch.Tensor, weights: torch.Tensor,
-                   chunk: int = 4096) -> torch.Tensor:
+                   chunk: int = 4096, dtype: str = "bf16") -> torch.Tensor:
     """Soft test-time routing: sum_e weights[:, e, None] * fc(conv_e(x)), every expert on every sample.
 
     With ``weights`` the scenario classifier's posterior this is the MMSE combination of the expert
-    estimates (the shared CE is linear); one-hot weights give ``estimate_routed``.  ``weights`` is (N, E)."""
+    estimates (the shared CE is linear); one-hot weights give ``estimate_routed``.  ``weights`` is (N, E).
+
+    ``dtype="fp8"``: p'_e = weights[:, e] rs_e, m = fma(p'_2, acc_2, fma(p'_1, acc_1, p'_0 acc_0)),
+    Y = bf16(fma(m, cs, b)) -- one-hot weights give ``estimate_routed(..., dtype="fp8")`` bit for bit."""
     E = len(convs)
     if weights.dim() != 2 or tuple(weights.shape) != (x.shape[0], E):
         raise ValueError(f"weights must be ({x.shape[0]}, {E}), got {tuple(weights.shape)}")
     w = weights.to(x.device, torch.float32)
     out = torch.zeros(x.shape[0], fc.FC.out_features, device=x.device, dtype=torch.float32)
+    if _infer_dtype(dtype) == "fp8":
+        W8, cs, b = _fp8_fc_operands(fc)
+        for s in range(0, x.shape[0], chunk):
+            xs = x[s:s + chunk].float()
+            m = None
+            for e in range(E):   # m = fma(p'_e, acc_e, m), p'_e = w_e rs_e (exact): the kernel's chain, expert 0 first
+                acc, rs = _fp8_rows_acc(convs[e](xs), W8)
+                pe = (w[s:s + chunk, e] * rs)[:, None]
+                m = _fma_f32(pe, acc, m)
+            out[s:s + chunk] = _fma_f32(m, cs[None, :], b).bfloat16().float()
+        return out
     for s in range(0, x.shape[0], chunk):
         xs = x[s:s + chunk].float()
         for e in range(E):
             out[s:s + chunk] += w[s:s + chunk, e, None] * fc(convs[e](xs)).float()
     return out
+
+
+# ---------------------------------------------------------------------- e4m3 test-time estimation (the definition)
+# dtype="fp8": the shared FC in OCP e4m3 with one power-of-two scale per operand row (sample, expert) and per output
+# channel.  No calibration pass, and a sample's estimate depends on that sample alone; scaling and dequantisation are
+# exact, so the only roundings are the e4m3 one, the accumulation, the bias fma and the bf16 store.  This is what
+# csrc/hip/conv.hip qd_bn_relu_rows_f8 + csrc/hip/gemm.hip qd_gemm_fwd_rows_f8 / qd_gemm_fwd_mix_rows_f8 compute
+# (train/infer.py); here in plain torch -- the CPU path and the oracle of the kernels' tests.
+INFER_DTYPES = ("bf16", "fp8")
+E4M3_MAX = 448.0
+SCALE_EXP_MIN, SCALE_EXP_MAX = -32, 32
+
+
+def _infer_dtype(dtype: str) -> str:
+    if dtype not in INFER_DTYPES:
+        raise ValueError(f"unknown estimator dtype {dtype!r}: one of {INFER_DTYPES}")
+    return dtype
+
+
+def scale_exponent(m: torch.Tensor) -> torch.Tensor:
+    """The scale exponent of vectors with maximum magnitude ``m`` (any shape, >= 0): the smallest integer e with
+    448 * 2^e >= m, clamped to [-32, 32]; m == 0 gives 0.  int32.  (448 = 0.875 * 2^9: with m = f 2^x, f in
+    [0.5, 1), e = x - 9, one more when f > 0.875 -- integer arithmetic on the float's own fields, no logarithm.)"""
+    m = m.detach().to(torch.float32)
+    f, x = torch.frexp(m)
+    e = (x - 9 + (f > 0.875).to(x.dtype)).clamp(SCALE_EXP_MIN, SCALE_EXP_MAX)
+    e = torch.where(torch.isinf(m), torch.full_like(e, SCALE_EXP_MAX), e)
+    return torch.where(m > 0, e, torch.zeros_like(e)).to(torch.int32)
+
+
+def quantise_rows_e4m3(h: torch.Tensor):
+    """Row-wise e4m3 quantisation of ``h`` (R, K): ``(h8, s)`` with h8[r] = e4m3_rne(h[r] * 2^-e_r) (float8_e4m3fn;
+    the scaling is exact, ONE rounding) and s[r] = 2^e_r fp32, e_r = scale_exponent(max |h[r]|)."""
+    hf = h.detach().to(torch.float32)
+    e = scale_exponent(hf.abs().amax(1))
+    one = torch.ones_like(e, dtype=torch.float32)
+    h8 = (hf * torch.ldexp(one, -e)[:, None]).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+    return h8, torch.ldexp(one, e)
+
+
+def _fp8_fc_operands(fc: nn.Module):
+    """(W8 (N, K) e4m3, cs (N,) = 2^f_j, bias (N,) as the bf16 value the kernels read) of the shared FC, quantised
+    per output channel from the fp32 master weight."""
+    W8, cs = quantise_rows_e4m3(fc.FC.weight.detach().float())
+    return W8, cs, fc.FC.bias.detach().to(torch.bfloat16).float()
+
+
+def _fp8_rows_acc(h: torch.Tensor, W8: torch.Tensor):
+    """Features ``h`` (R, K) of one expert -> (acc (R, N) fp32, rs (R,)): the rows rounded to bf16 (the FC operand
+    the eval BN + ReLU apply writes), quantised row-wise, and their e4m3 products with W8 summed.  The products are
+    exact; the sum is formed in float64 (exact for these sizes) and rounded ONCE to fp32, so a row's accumulator
+    does not depend on the batch it is computed in."""
+    h8, rs = quantise_rows_e4m3(h.to(torch.bfloat16))
+    return (h8.to(torch.float64) @ W8.to(torch.float64).t()).to(torch.float32), rs
+
+
+def _fma_f32(a: torch.Tensor, b: torch.Tensor, c: Optional[torch.Tensor]) -> torch.Tensor:
+    """fp32 fma(a, b, c) (c None: the rounded product) through float64: the product of two fp32 values is exact
+    there."""
+    p = a.to(torch.float64) * b.to(torch.float64)
+    return (p if c is None else p + c.to(torch.float64)).to(torch.float32)
 
 
 class HDCEStep:

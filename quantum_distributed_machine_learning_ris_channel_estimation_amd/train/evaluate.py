@@ -29,7 +29,7 @@ from ..data.baselines import lmmse_estimate
 from ..data.channel import generate_mixed, pack_channel, pack_pilots
 from ..models.estimators import Conv_P128, FC_P128, NMSELoss, QSC_P128, SC_P128
 from . import checkpoint as ck
-from .engine import estimate_mixed, estimate_routed
+from .engine import INFER_DTYPES, estimate_mixed, estimate_routed
 
 
 @torch.no_grad()
@@ -100,6 +100,7 @@ class model_val:
         self.qsc_noise_model()   # (refuses noise rates without qsc_shots)
         self._post_stats()
         self._routing()
+        self._dtype()
         self.results: Dict[str, List[float]] = {}
 
     def load_model_state_dict(self, model, filepath, fallback_key=None):
@@ -128,6 +129,11 @@ class model_val:
         if self.routing not in ROUTINGS:
             raise ValueError(f"unknown routing {self.routing!r}: one of {ROUTINGS}")
         return self.routing
+
+    def _dtype(self) -> str:
+        if self.dtype not in INFER_DTYPES:
+            raise ValueError(f"unknown dtype {self.dtype!r}: one of {INFER_DTYPES}")
+        return self.dtype
 
     # ------------------------------------------------------------------ loading
     def _dir(self) -> str:
@@ -198,6 +204,7 @@ class model_val:
                "nmse_mmse": float(criterion(pack_channel(HMMSE), perf)),
                "nmse_lmmse": float(criterion(pack_channel(HLMMSE), perf))}
         soft = self._routing() == "soft"
+        dt = self._dtype()   # ("fp8": the shared FC in e4m3 -- the engine's kernels, or engine.py's torch definition)
         if soft:
             for clf in (sc, qsc):
                 nc = None if clf is None else clf.FC.out_features if isinstance(clf, SC_P128) else clf.n_classes
@@ -205,7 +212,7 @@ class model_val:
                     raise ValueError(f"soft routing: a classifier of {nc} classes cannot weight {len(convs)} experts")
         eng = self._hip_engine(sc, qsc, convs, fc)
         if soft:   # the oracle row: hard routing by the true scenario
-            Hor = eng.estimate(x, ind) if eng is not None else estimate_routed(convs, fc, x, ind.to(x.device))
+            Hor = eng.estimate(x, ind) if eng is not None else estimate_routed(convs, fc, x, ind.to(x.device), dtype=dt)
             out["nmse_oracle"] = float(criterion(Hor, perf))
         for tag, clf in (("classical", sc), ("quantum", qsc)):
             if clf is None:
@@ -242,10 +249,10 @@ class model_val:
                     eng.load_bn_stats(convs)
                 Hhat = eng.estimate(x, pred)
             else:
-                Hhat = estimate_routed(convs, fc, x, pred)
+                Hhat = estimate_routed(convs, fc, x, pred, dtype=dt)
             if soft:   # the experts under the posterior the prediction was the arg-max of (same shots, noise, seed)
                 wts = logp.float().exp()
-                Hs = eng.estimate_mixed(x, wts) if eng is not None else estimate_mixed(convs, fc, x, wts)
+                Hs = eng.estimate_mixed(x, wts) if eng is not None else estimate_mixed(convs, fc, x, wts, dtype=dt)
                 out[f"nmse_{tag}_soft"] = float(criterion(Hs, perf))
             if saved is not None:
                 restore_bn(convs, saved)
@@ -265,13 +272,13 @@ class model_val:
         # the sweep itself adapts are handed over by load_bn_stats)
         mods = [m for m in (sc, qsc, *convs, fc) if m is not None]
         ver = tuple(t._version for m in mods for t in m.parameters())
-        key = (tuple(mods), ver)
+        key = (tuple(mods), ver, self._dtype())
         old = getattr(self, "_eng_key", None)
         if old is None or len(old[0]) != len(key[0]) or any(a is not b for a, b in zip(old[0], key[0])) \
-                or old[1] != ver:
+                or old[1:] != key[1:]:
             from .infer import HIPInference
             self._eng = HIPInference(convs, fc, self.Pilot_num, self.device, sc=sc,
-                                     qsc=qsc if (qsc is not None and qsc.use_quantum) else None)
+                                     qsc=qsc if (qsc is not None and qsc.use_quantum) else None, dtype=key[2])
             self._eng_key = key
         return self._eng
 

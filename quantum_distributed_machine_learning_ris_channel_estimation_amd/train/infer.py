@@ -16,6 +16,14 @@ Here, per chunk of ``chunk`` samples (one static buffer set; graph-friendly, no 
               expert features: the top-1 routing is fused into the GEMM (no permutation, no scatter)
   mixed FC    (soft routing) the same GEMM over ALL expert rows, the classifier's posterior combining each
               sample's three product rows in its epilogue (``estimate_mixed``, csrc/hip/gemm.hip EPI_MIX)
+
+``dtype="fp8"``: the shared FC in OCP e4m3, the precision the fp8 estimator is trained in (``engine``'s definition:
+``quantise_rows_e4m3`` and the fp8 estimates).  The last expert launch becomes the row-quantising BN + ReLU apply
+(csrc/hip/conv.hip qd_bn_relu_rows_f8: every FC-operand row (sample, expert) gets its own power-of-two scale, the bf16
+operand is never written), the weights are quantised per output channel once (and by ``refresh``), and the routed /
+mixed FC are qd_gemm_fwd_rows_f8 / qd_gemm_fwd_mix_rows_f8, which dequantise by row and column in their epilogues.
+Nothing is calibrated, so a sample's estimate does not depend on its chunk or its neighbours, and test-time BN
+adaptation needs no extra step.
 """
 from __future__ import annotations
 
@@ -35,13 +43,16 @@ _p, _i, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
 
 class HIPInference:
     def __init__(self, convs: Sequence[nn.Module], fc: nn.Module, pilot_num: int, device, chunk: int = 2304,
-                 sc: Optional[SC_P128] = None, qsc: Optional[QSC_P128] = None):
+                 sc: Optional[SC_P128] = None, qsc: Optional[QSC_P128] = None, dtype: str = "bf16"):
         from ..ops.conv import ConvStackHIP
         from ..ops.qsc import QSCStepHIP
         from ..ops.sc import SCStepHIP
-        from .engine import HDCEModel
+        from .engine import HDCEModel, _infer_dtype
         self.dev = torch.device(device)
         self.chunk = chunk
+        self.dtype = _infer_dtype(dtype)
+        if self.dtype == "fp8" and chunk % 144:
+            raise ValueError(f"HIPInference(dtype='fp8'): chunk {chunk} is not a multiple of 144 (whole GEMM tiles)")
         self.H, self.W = pilot_grid(pilot_num)
         self.E = len(convs)
         self.pilot_num = pilot_num
@@ -56,6 +67,12 @@ class HIPInference:
         self.conv = ConvStackHIP(m, 1, chunk)
         self.W_lp = m.fc_w.detach().to(torch.bfloat16).contiguous()
         self.b_lp = m.fc_b.detach().to(torch.bfloat16).contiguous()
+        self.W8 = self.cs = None
+        if self.dtype == "fp8":
+            self.conv.rows_f8 = True    # (eval forwards return the e4m3 rows; their scales in conv.rs)
+            self._quantise_fc()
+            # FwdM8P (MX MFMA, producer waves) where K allows, else the non-scaled e4m3 MFMA
+            self.f8_cfg = 2 if self.W8.shape[1] % 256 == 0 else 0
         # classifiers: private copies whose parameters live in flat spaces (the kernels' layout)
         self.sc = self.qsc = None
         if sc is not None:
@@ -76,6 +93,16 @@ class HIPInference:
         self._gather = nat.fn(nat.hip_lib(), "qd_gather_step", [_p, _p, _l, _p, _p, _p, _l, _i, _i, _i, _i, _p])
         self._plane = plane
 
+    def _quantise_fc(self) -> None:
+        """The e4m3 FC weight with one power-of-two scale per output channel, from the fp32 master."""
+        from .engine import quantise_rows_e4m3
+        W8, cs = quantise_rows_e4m3(self.model.fc_w.detach())
+        if self.W8 is None:
+            self.W8, self.cs = W8.contiguous(), cs.contiguous()
+        else:
+            self.W8.copy_(W8)
+            self.cs.copy_(cs)
+
     @torch.no_grad()
     def refresh(self, convs: Sequence[nn.Module], fc: nn.Module) -> None:
         """Reload the estimator weights and BN statistics (e.g. once per epoch of a training run: the
@@ -85,6 +112,8 @@ class HIPInference:
         self.model.fc.load_state_dict(fc.state_dict())
         self.W_lp.copy_(self.model.fc_w.detach())
         self.b_lp.copy_(self.model.fc_b.detach())
+        if self.dtype == "fp8":
+            self._quantise_fc()
 
     @torch.no_grad()
     def load_bn_stats(self, convs: Sequence[nn.Module]) -> None:
@@ -203,7 +232,7 @@ class HIPInference:
         """Routed estimate (N, 2048) fp32: sample i through expert ``expert[i]`` and the shared FC.  Every
         expert's conv stack runs on every sample by design (see the module docstring); ``estimate_mixed`` relies
         on it: its GEMM reads all the rows (b, e) this one selects from."""
-        from ..ops.fc import gemm_fwd
+        from ..ops.fc import gemm_fwd, gemm_fwd_rows_f8
         x = x.contiguous().float()
         N = x.shape[0]
         expert = expert.to(self.dev, torch.int64)
@@ -213,7 +242,11 @@ class HIPInference:
             self._load(x, lo, n)
             self.pred[:n].copy_(expert[lo:lo + n])
             h = self.conv.forward(self.x1, training=False)            # (chunk * E, 32 H W) bf16, rows (b, e)
-            gemm_fwd(h, self.W_lp, self.b_lp, out=self.Y, expert=self.pred, n_experts=self.E)
+            if self.dtype == "fp8":                                   # (h: e4m3 rows, conv.rs their scales)
+                gemm_fwd_rows_f8(h, self.W8, self.conv.rs, self.cs, self.b_lp, out=self.Y, cfg=self.f8_cfg,
+                                 expert=self.pred, n_experts=self.E)
+            else:
+                gemm_fwd(h, self.W_lp, self.b_lp, out=self.Y, expert=self.pred, n_experts=self.E)
             out[lo:lo + n].copy_(self.Y[:n])
         return out
 
@@ -222,8 +255,9 @@ class HIPInference:
         """Soft-routed estimate (N, 2048) fp32: sum_e weights[i, e] * (expert e of sample i through the shared
         FC), the combination in the FC GEMM's epilogue (ops.fc.gemm_fwd_mix; the bias is added once, so this is
         ``engine.estimate_mixed`` for weights that sum to 1).  ``weights`` (N, E) fp32, e.g. ``exp(logp)`` of
-        ``classify(..., return_logp=True)``.  The chunk must be a multiple of 48 (whole GEMM tiles)."""
-        from ..ops.fc import gemm_fwd_mix
+        ``classify(..., return_logp=True)``.  The chunk must be a multiple of 48 (whole GEMM tiles; ``dtype="fp8"``:
+        of 144, checked at construction)."""
+        from ..ops.fc import gemm_fwd_mix, gemm_fwd_mix_rows_f8
         x = x.contiguous().float()
         N = x.shape[0]
         if weights.dim() != 2 or tuple(weights.shape) != (N, self.E):
@@ -237,6 +271,10 @@ class HIPInference:
             if n < self.chunk:   # (the tail repeats sample lo, as _load's: its outputs are dropped)
                 self.wmix[n:].copy_(weights[lo:lo + 1].expand(self.chunk - n, self.E))
             h = self.conv.forward(self.x1, training=False)            # (chunk * E, 32 H W) bf16, rows (b, e)
-            gemm_fwd_mix(h, self.W_lp, self.b_lp, self.wmix, out=self.Y)
+            if self.dtype == "fp8":
+                gemm_fwd_mix_rows_f8(h, self.W8, self.conv.rs, self.cs, self.b_lp, self.wmix, out=self.Y,
+                                     cfg=self.f8_cfg)
+            else:
+                gemm_fwd_mix(h, self.W_lp, self.b_lp, self.wmix, out=self.Y)
             out[lo:lo + n].copy_(self.Y[:n])
         return out

@@ -32,6 +32,8 @@ def main():
                     "and run the sweep on the average (written under <out>/swa, and <out>/swa_bn_adapt with --bn-adapt)")
     ap.add_argument("--routing", default="hard", choices=["hard", "soft"], help="soft: the sweeps also report the "
                     "posterior-weighted (nmse_*_soft) and oracle-routed (nmse_oracle) rows")
+    ap.add_argument("--eval-fp8", action="store_true", help="also run the sweep with the shared FC in e4m3 "
+                    "(EvalConfig.dtype=fp8: per-row / per-channel power-of-two scales; written under <out>/eval_fp8)")
     a = ap.parse_args()
     from quantum_distributed_machine_learning_ris_channel_estimation_amd.train.evaluate import model_val
     from quantum_distributed_machine_learning_ris_channel_estimation_amd.train.runner import Y2HRunner
@@ -75,6 +77,14 @@ def main():
         t0 = time.time()
         mva.test_for_CE_P128_for_all_scenarios()
         t["eval_bn_adapt_s"] = time.time() - t0
+    if a.eval_fp8:
+        mv8 = model_val(workspace=a.workspace, results_dir=os.path.join(a.out, "eval_fp8"), data_len_for_test=a.test_len,
+                        training_data_len=a.data_len, batch_size_DML=a.batch, n_qubits=a.qubits, routing=a.routing,
+                        dtype="fp8")
+        mv8.epoch_tag = mv.epoch_tag
+        t0 = time.time()
+        mv8.test_for_CE_P128_for_all_scenarios()
+        t["eval_fp8_s"] = time.time() - t0
     if a.swa_epochs > 0:
         for sub, bn in (("swa", False),) + ((("swa_bn_adapt", True),) if a.bn_adapt else ()):
             mvs = model_val(workspace=a.workspace, results_dir=os.path.join(a.out, sub), data_len_for_test=a.test_len,
