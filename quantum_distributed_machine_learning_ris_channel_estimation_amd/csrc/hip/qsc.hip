@@ -540,7 +540,7 @@ static int launch_pre_bwd(const float* x, const float* flat, Offs o, const float
 
 QD_API int qd_qsc_pre_fwd(const float* x, const float* flat, const int* offs, float* angles, int B, int n, int H, int W,
                           int grid, void* stream) {
-  if (n > 16 || B <= 0) return (int)hipErrorInvalidValue;
+  if (n < 1 || n > 16 || B <= 0 || grid <= 0) return (int)hipErrorInvalidValue;
   Offs o{offs[0], offs[1], offs[2], offs[3], offs[4], offs[5], offs[6]};
   hipStream_t s = (hipStream_t)stream;
   if (H == 16 && W == 8) return launch_pre_fwd<16, 8>(x, flat, o, angles, B, n, grid, s);
@@ -551,7 +551,7 @@ QD_API int qd_qsc_pre_fwd(const float* x, const float* flat, const int* offs, fl
 // slab: (grid, offs[6]) floats; row layout = flat layout starting at offs[0].
 QD_API int qd_qsc_pre_bwd(const float* x, const float* flat, const int* offs, const float* dang, float* slab, int B,
                           int n, int H, int W, int grid, void* stream) {
-  if (n > 16 || B <= 0 || qsc_smem(H, W, true, n) > 160 * 1024) return (int)hipErrorInvalidValue;
+  if (n < 1 || n > 16 || B <= 0 || grid <= 0 || qsc_smem(H, W, true, n) > 160 * 1024) return (int)hipErrorInvalidValue;
   Offs o{offs[0], offs[1], offs[2], offs[3], offs[4], offs[5], offs[6]};
   hipStream_t s = (hipStream_t)stream;
   if (H == 16 && W == 8) return launch_pre_bwd<16, 8>(x, flat, o, dang, slab, B, n, grid, s);
@@ -562,6 +562,7 @@ QD_API int qd_qsc_pre_bwd(const float* x, const float* flat, const int* offs, co
 QD_API int qd_qsc_head(const float* E, const float* wc, const float* bc, const long* labels, float* dE, float* dwc,
                        float* dbc, float* loss, float* loss_acc, float* skip, int skip_add, int accumulate, int B,
                        int n, int C, void* stream) {
+  if (B < 1) return (int)hipErrorInvalidValue;   // (the mean over no sample: 0 * inf)
   hipStream_t s = (hipStream_t)stream;
 #define QD_HEAD(NN, CC)                                                                                      \
   if (n == NN && C == CC) {                                                                                 \
@@ -618,6 +619,7 @@ __global__ void __launch_bounds__(256) qsc_infer_head_kernel(const float* __rest
 
 QD_API int qd_qsc_infer_head(const float* E, const float* wc, const float* bc, float* logp, long* pred, int B, int n,
                              int C, void* stream) {
+  if (B < 1) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   const int grid = (B + 255) / 256;
 #define QD_IH(NN, CC)                                                                                      \

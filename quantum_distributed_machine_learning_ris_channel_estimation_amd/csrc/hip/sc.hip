@@ -436,6 +436,7 @@ QD_API int qd_sc_bwd(const float* x, const float* flat, const int* offs, int B, 
 
 QD_API int qd_sc_finish(const float* part, int nblk, int B, float* out, float* loss_acc, float* skip, int skip_add,
                         void* stream) {
+  if (nblk < 1 || B < 1) return (int)hipErrorInvalidValue;   // (no partial to sum, or the mean over no sample)
   hipLaunchKernelGGL(sc_finish_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, part, nblk, 1.f / (float)B, out,
                      loss_acc, skip, skip_add);
   return (int)hipGetLastError();
