@@ -220,6 +220,126 @@ def gemm_fwd_mix_rows_f8(A8: torch.Tensor, W8: torch.Tensor, rs: torch.Tensor, c
     return Y
 
 
+# ---------------------------------------------------------------- skinny forwards (1 <= M <= 16 output rows)
+# csrc/hip/gemm_skinny.hip: the four test-time forwards above as a weight stream over the whole chip, for a request of
+# 1-16 samples.  N % 16 == 0, K % 512 == 0 (gemm_fwd_skinny_ok); output row i is bit for bit the same at every M.
+_SKINNY_WS = {}
+
+
+def gemm_fwd_skinny_ok(M: int, N: int, K: int, fp8: bool = False) -> bool:
+    return bool(_gemm_fn("qd_gemm_fwd_skinny_ok", [_i, _i, _i, _i])(M, N, K, int(fp8)))
+
+
+def gemm_skinny_workspace(N: int, K: int, device, cached: bool = True) -> torch.Tensor:
+    """The skinny forwards' workspace for (N, K): ticket words and partial slabs, zeroed here once -- every call
+    leaves it as it found it.  One workspace serves one stream at a time; ``cached`` (what the forwards use when no
+    ``ws`` is given): one per (device, N, K)."""
+    nb = int(nat.fn(nat.hip_lib(), "qd_gemm_fwd_skinny_ws_bytes", [_i, _i], ctypes.c_long)(N, K))
+    if nb <= 0:
+        raise ValueError(f"gemm_fwd_skinny: (N, K) = {(N, K)} not supported (N % 16 == 0, K % 512 == 0)")
+    device = torch.device(device)
+    if not cached:
+        return torch.zeros(nb, dtype=torch.uint8, device=device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (device, N, K)
+    if key not in _SKINNY_WS:
+        _SKINNY_WS[key] = torch.zeros(nb, dtype=torch.uint8, device=device)
+    return _SKINNY_WS[key]
+
+
+def _skinny_common(A, W, b, M, out, ws, fp8):
+    K = A.shape[1]
+    N = W.shape[0]
+    dt = torch.float8_e4m3fn if fp8 else torch.bfloat16
+    assert A.dtype == W.dtype == dt and A.is_contiguous() and W.is_contiguous() and W.shape[1] == K
+    assert W.device == A.device
+    assert b is None or (b.dtype == torch.bfloat16 and b.numel() == N and b.is_contiguous())
+    if not gemm_fwd_skinny_ok(M, N, K, fp8):
+        raise ValueError(f"gemm_fwd_skinny: shape {(M, N, K)} not supported (1 <= M <= 16, N % 16 == 0, K % 512 == 0)")
+    Y = out if out is not None else torch.empty(M, N, device=A.device, dtype=torch.bfloat16)
+    assert Y.dtype == torch.bfloat16 and Y.shape[0] >= M and Y.shape[1] == N and Y.is_contiguous()
+    if ws is None:
+        ws = gemm_skinny_workspace(N, K, A.device)
+    return N, K, Y, ws
+
+
+def _skinny_expert(A, expert, n_experts):
+    if expert is None:
+        if n_experts != 1:
+            raise ValueError("gemm_fwd_skinny: expert indices are required unless n_experts == 1")
+        return A.shape[0]
+    assert expert.dtype == torch.int64 and expert.is_contiguous() and expert.device == A.device
+    M = expert.numel()
+    assert A.shape[0] >= M * n_experts
+    return M
+
+
+def gemm_fwd_skinny(A: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None, expert: Optional[torch.Tensor] = None, n_experts: int = 1,
+                    ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gemm_fwd``'s Y = A W^T (+ b) with optional expert-routed rows, for 1 <= M <= 16 output rows."""
+    M = _skinny_expert(A, expert, n_experts)
+    N, K, Y, ws = _skinny_common(A, W, b, M, out, ws, False)
+    f = _gemm_fn("qd_gemm_fwd_skinny", [_p, _p, _p, _p, _i, _i, _i, _p, _i, _p, _p])
+    nat.check(f(nat.ptr(A), nat.ptr(W), nat.ptr(b) if b is not None else None, nat.ptr(Y), M, N, K,
+                nat.ptr(expert) if expert is not None else None, n_experts, nat.ptr(ws), nat.stream_ptr(A.device)),
+              "gemm_fwd_skinny")
+    return Y
+
+
+def gemm_fwd_skinny_mix(A: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor], weights: torch.Tensor,
+                        out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gemm_fwd_mix`` for 1 <= M <= 16 output rows (A holds the 3 M rows (i, e), ``weights`` (M, 3) fp32)."""
+    assert weights.dim() == 2 and weights.dtype == torch.float32 and weights.is_contiguous()
+    assert weights.device == A.device
+    M, E = weights.shape
+    if E != 3:
+        raise ValueError(f"gemm_fwd_skinny_mix: 3 experts, got {E}")
+    assert A.shape[0] >= M * E
+    N, K, Y, ws = _skinny_common(A, W, b, M, out, ws, False)
+    f = _gemm_fn("qd_gemm_fwd_skinny_mix", [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p])
+    nat.check(f(nat.ptr(A), nat.ptr(W), nat.ptr(b) if b is not None else None, nat.ptr(weights), nat.ptr(Y), M, N, K,
+                E, nat.ptr(ws), nat.stream_ptr(A.device)), "gemm_fwd_skinny_mix")
+    return Y
+
+
+def gemm_fwd_skinny_rows_f8(A8: torch.Tensor, W8: torch.Tensor, rs: torch.Tensor, cs: torch.Tensor,
+                            b: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                            expert: Optional[torch.Tensor] = None, n_experts: int = 1,
+                            ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gemm_fwd_rows_f8`` for 1 <= M <= 16 output rows (``rs`` may be longer than A8 has rows in use)."""
+    M = _skinny_expert(A8, expert, n_experts)
+    N, K, Y, ws = _skinny_common(A8, W8, b, M, out, ws, True)
+    assert rs.dtype == cs.dtype == torch.float32 and rs.is_contiguous() and cs.is_contiguous()
+    assert rs.numel() >= M * n_experts and cs.numel() == N and rs.device == cs.device == A8.device
+    f = _gemm_fn("qd_gemm_fwd_skinny_rows_f8", [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _p, _p])
+    nat.check(f(nat.ptr(A8), nat.ptr(W8), nat.ptr(rs), nat.ptr(cs), nat.ptr(b) if b is not None else None, nat.ptr(Y),
+                M, N, K, nat.ptr(expert) if expert is not None else None, n_experts, nat.ptr(ws),
+                nat.stream_ptr(A8.device)), "gemm_fwd_skinny_rows_f8")
+    return Y
+
+
+def gemm_fwd_skinny_mix_rows_f8(A8: torch.Tensor, W8: torch.Tensor, rs: torch.Tensor, cs: torch.Tensor,
+                                b: Optional[torch.Tensor], weights: torch.Tensor, out: Optional[torch.Tensor] = None,
+                                ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gemm_fwd_mix_rows_f8`` for 1 <= M <= 16 output rows."""
+    assert weights.dim() == 2 and weights.dtype == torch.float32 and weights.is_contiguous()
+    assert weights.device == A8.device
+    M, E = weights.shape
+    if E != 3:
+        raise ValueError(f"gemm_fwd_skinny_mix_rows_f8: 3 experts, got {E}")
+    assert A8.shape[0] >= M * E
+    N, K, Y, ws = _skinny_common(A8, W8, b, M, out, ws, True)
+    assert rs.dtype == cs.dtype == torch.float32 and rs.is_contiguous() and cs.is_contiguous()
+    assert rs.numel() >= M * E and cs.numel() == N and rs.device == cs.device == A8.device
+    f = _gemm_fn("qd_gemm_fwd_skinny_mix_rows_f8", [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p])
+    nat.check(f(nat.ptr(A8), nat.ptr(W8), nat.ptr(rs), nat.ptr(cs), nat.ptr(b) if b is not None else None,
+                nat.ptr(weights), nat.ptr(Y), M, N, K, E, nat.ptr(ws), nat.stream_ptr(A8.device)),
+              "gemm_fwd_skinny_mix_rows_f8")
+    return Y
+
+
 def gemm_nt_f8(P8: torch.Tensor, Q8: torch.Tensor, sP: torch.Tensor, sQ: torch.Tensor, out: Optional[torch.Tensor] = None,
                out_dtype=torch.bfloat16, cfg: int = 1) -> torch.Tensor:
     """C (I, J) = sP sQ P8 Q8^T on the MX-scaled e4m3 MFMA (csrc/hip/gemm.hip qd_gemm_nt_f8): P8 (I, K), Q8 (J, K)

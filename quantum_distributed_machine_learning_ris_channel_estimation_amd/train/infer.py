@@ -24,6 +24,11 @@ operand is never written), the weights are quantised per output channel once (an
 mixed FC are qd_gemm_fwd_rows_f8 / qd_gemm_fwd_mix_rows_f8, which dequantise by row and column in their epilogues.
 Nothing is calibrated, so a sample's estimate does not depend on its chunk or its neighbours, and test-time BN
 adaptation needs no extra step.
+
+``HIPInference.session(batch, ...)`` (``InferSession``): the low-latency path for ONE request of 1..16 samples -- a
+pilot frame of the system's 9 user streams, not a sweep chunk.  Input packing, classifier, routing, the experts and
+the FC are one captured graph on one stream; the FC is the skinny forward (csrc/hip/gemm_skinny.hip), which streams
+the weight once over the whole chip instead of tiling 144 rows.
 """
 from __future__ import annotations
 
@@ -102,6 +107,11 @@ class HIPInference:
         else:
             self.W8.copy_(W8)
             self.cs.copy_(cs)
+
+    def session(self, batch: int, which: Optional[str] = "quantum", routing: str = "hard", shots: int = 0,
+                seed: int = 0, noise=None, trajectories: int = 1) -> "InferSession":
+        """A low-latency estimate path for requests of exactly ``batch`` (1..16) samples: see ``InferSession``."""
+        return InferSession(self, batch, which, routing, shots, seed, noise, trajectories)
 
     @torch.no_grad()
     def refresh(self, convs: Sequence[nn.Module], fc: nn.Module) -> None:
@@ -278,3 +288,168 @@ class HIPInference:
                 gemm_fwd_mix(h, self.W_lp, self.b_lp, self.wmix, out=self.Y)
             out[lo:lo + n].copy_(self.Y[:n])
         return out
+
+
+class InferSession:
+    """One request of ``batch`` (1..16) samples from pilots to channel as ONE captured graph on one stream.
+
+    ``which``: "quantum" / "classical" -- the engine's classifier runs in the graph and routes on the device; None:
+    the caller supplies ``expert=`` (hard) or ``weights=`` (soft) to ``run``.  ``routing``: "hard" (top-1, the routed
+    skinny FC reads ``pred`` in place) or "soft" (``wmix = exp(logp)`` on the device, the mixing skinny FC).  ``shots``
+    / ``seed`` / ``noise`` / ``trajectories`` as ``classify`` ("quantum" only): the shot stream is keyed by ``seed`` and
+    a device call counter that the graph advances by one per ``run`` (run r of a session draws what ``classify`` draws
+    for chunk r), so repeated runs draw fresh shots and a fresh session with the same seed repeats the sequence.
+
+    The session owns the static buffers (input, x1, pred, logp, wmix, Y, the skinny FC's workspace), a
+    ``ConvStackHIP(model, 1, batch)`` and a classifier step at ``batch`` over the ENGINE's classifier module and flat
+    space; the estimator model, W_lp, b_lp, W8 and cs are the engine's, so ``refresh`` / ``load_bn_stats`` /
+    ``recalibrate_bn`` there reach the next ``run``.  No kernel of the chain needs padding at 1..16 samples, and none
+    mixes samples (BN runs on its running statistics), so a sample's outputs do not depend on ``batch``.
+
+    ``run(x)`` copies x into the static input, replays the graph and returns views of the static outputs, valid until
+    the next ``run``: H (batch, 2048) bf16, pred (batch,) int64, logp (batch, C) fp32 (None when ``which`` is None;
+    pred is None too for soft routing without a classifier).  No host synchronisation.  Everything refused is a
+    ValueError at construction or before the replay, with nothing launched.  The graph executable follows
+    utils/profiling.py's rule (``close``: parked, destroyed at exit)."""
+
+    def __init__(self, eng: HIPInference, batch: int, which: Optional[str], routing: str, shots: int, seed: int,
+                 noise, trajectories: int):
+        from ..ops.conv import ConvStackHIP
+        from ..ops.fc import gemm_fwd_skinny_ok, gemm_skinny_workspace
+        from ..ops.qsc import QSCStepHIP
+        from ..ops.quantum import resolve_measure
+        from ..ops.sc import SCStepHIP
+        from ..utils.profiling import GraphedStep
+        if not isinstance(batch, int) or not 1 <= batch <= 16:
+            raise ValueError(f"session: batch must be 1..16, got {batch!r}")
+        if which not in ("quantum", "classical", None):
+            raise ValueError(f"session: which must be 'quantum', 'classical' or None, got {which!r}")
+        if routing not in ("hard", "soft"):
+            raise ValueError(f"session: routing must be 'hard' or 'soft', got {routing!r}")
+        if shots and which != "quantum":
+            raise ValueError("shots apply to the quantum classifier only")
+        if noise is not None and not shots:
+            raise ValueError("noise needs shots")
+        clf = None if which is None else (eng.sc if which == "classical" else eng.qsc)
+        if which is not None and clf is None:
+            raise ValueError(f"session: no {which} classifier loaded")
+        self.C = None if which is None else (3 if which == "classical" else eng.qsc.C)
+        if routing == "soft" and which is not None and self.C != eng.E:
+            raise ValueError(f"session: soft routing needs one class per expert ({self.C} classes, {eng.E} experts)")
+        if routing == "soft" and eng.E != 3:
+            raise ValueError(f"session: the mixing FC takes 3 experts, the engine has {eng.E}")
+        N, K = eng.W_lp.shape
+        fp8 = eng.dtype == "fp8"
+        if not gemm_fwd_skinny_ok(batch, N, K, fp8):
+            raise ValueError(f"session: the skinny FC does not cover (N, K) = {(N, K)} (N % 16 == 0, K % 512 == 0)")
+        if shots:   # (what infer would refuse, refused here and with its exception)
+            resolve_measure("adjoint", shots, noise, trajectories if noise is not None else 1, None, eng.qsc.n,
+                            eng.qsc.L, "hip", eng.dev)
+        self.eng, self.batch, self.which, self.routing, self.fp8 = eng, batch, which, routing, fp8
+        self.shots, self.seed, self.noise, self.trajectories = int(shots), int(seed), noise, trajectories
+        dev = eng.dev
+        self.conv = ConvStackHIP(eng.model, 1, batch)
+        self.conv.rows_f8 = fp8
+        self.clf = None
+        if which == "classical":
+            self.clf = SCStepHIP(eng._sc_mod, eng.sc.space)
+        elif which == "quantum":
+            self.clf = QSCStepHIP(eng._qsc_mod, eng.qsc.space, batch, n_groups=1)
+        self.x = torch.zeros(batch, 2, eng.H, eng.W, device=dev)
+        self.x1 = torch.zeros(batch, 2 * eng.E, eng.H, eng.W, device=dev)
+        self.idx = torch.arange(batch, dtype=torch.int64, device=dev)
+        self.pred = torch.zeros(batch, dtype=torch.int64, device=dev)
+        self.logp = None if which is None else torch.zeros(batch, self.C, device=dev)
+        self.wmix = torch.zeros(batch, eng.E, device=dev)
+        self.Y = torch.zeros(batch, N, device=dev, dtype=torch.bfloat16)
+        self.ws = gemm_skinny_workspace(N, K, dev, cached=False)
+        self.ctr = torch.zeros((), dtype=torch.int64, device=dev) if shots else None
+        self._sc_fwd = nat.fn(nat.hip_lib(), "qd_sc_fwd", [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p,
+                                                            _p]) if which == "classical" else None
+        self.launches = []
+        self._record = True
+        self._step = GraphedStep(self._chain, warmup=1)
+        with torch.no_grad():
+            self._step.capture()
+        if self.ctr is not None:
+            self.ctr.zero_()         # (the warm-up advanced it)
+        torch.cuda.current_stream(dev).synchronize()
+
+    def _note(self, *names: str) -> None:
+        if self._record:
+            self.launches.extend(names)
+
+    def _chain(self) -> None:
+        """The request's launches, in order, on the current stream (captured once)."""
+        from ..ops.fc import (gemm_fwd_skinny, gemm_fwd_skinny_mix, gemm_fwd_skinny_mix_rows_f8,
+                              gemm_fwd_skinny_rows_f8)
+        from ..ops.quantum import counter_add
+        eng, st = self.eng, nat.stream_ptr(self.eng.dev)
+        nat.check(eng._gather(nat.ptr(self.idx), nat.ptr(self.x), 0, nat.ptr(self.x1), None, None, 0, eng.E, 1,
+                              self.batch, eng._plane, st), "gather(x1)")
+        self._note("gather: x -> experts-in-channels x1")
+        if self.which == "classical":
+            sc = self.clf
+            nat.check(self._sc_fwd(nat.ptr(self.x), nat.ptr(sc.space.flat), sc.offs, None, self.batch, sc.SPB_FWD, sc.H,
+                                   sc.W, None, None, None, None, None, None, nat.ptr(self.logp), nat.ptr(self.pred), st),
+                      "sc_fwd")
+            self._note("sc_fwd: SC_P128 forward, log-posterior and argmax")
+        elif self.which == "quantum":
+            self.clf.infer(self.x, self.pred, logp=self.logp, shots=self.shots, seed=self.seed,
+                           counter=self.ctr if self.ctr is not None else 0, noise=self.noise,
+                           trajectories=self.trajectories)
+            self._note("qsc preprocess forward", "circuit forward" + (" (measured)" if self.shots else ""),
+                       "qsc head: log-posterior and argmax")
+            if self.ctr is not None:
+                counter_add(self.ctr, 1)
+                self._note("counter += 1")
+        if self.routing == "soft" and self.which is not None:
+            torch.exp(self.logp, out=self.wmix)
+            self._note("wmix = exp(logp)")
+        h = self.conv.forward(self.x1, training=False)
+        self._note("conv weight pack", "conv1", "conv2 (+ BN1)", "conv3 (+ BN2)")
+        self._note(*(("BN tail", "BN3 + ReLU + e4m3 row quantisation") if self.fp8 else ("BN3 + ReLU apply with the BN tail",)))
+        if self.routing == "hard":
+            if self.fp8:
+                gemm_fwd_skinny_rows_f8(h, eng.W8, self.conv.rs, eng.cs, eng.b_lp, out=self.Y, expert=self.pred,
+                                        n_experts=eng.E, ws=self.ws)
+            else:
+                gemm_fwd_skinny(h, eng.W_lp, eng.b_lp, out=self.Y, expert=self.pred, n_experts=eng.E, ws=self.ws)
+        elif self.fp8:
+            gemm_fwd_skinny_mix_rows_f8(h, eng.W8, self.conv.rs, eng.cs, eng.b_lp, self.wmix, out=self.Y, ws=self.ws)
+        else:
+            gemm_fwd_skinny_mix(h, eng.W_lp, eng.b_lp, self.wmix, out=self.Y, ws=self.ws)
+        self._note("skinny FC (" + ("routed" if self.routing == "hard" else "mix") + (", e4m3" if self.fp8 else ", bf16") + ")")
+        self._record = False
+
+    @torch.no_grad()
+    def run(self, x: torch.Tensor, expert: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None):
+        eng = self.eng
+        if self._step is None:
+            raise ValueError("session: closed")
+        if tuple(x.shape) != tuple(self.x.shape):
+            raise ValueError(f"session: input must be {tuple(self.x.shape)}, got {tuple(x.shape)}")
+        if self.which is None:
+            if self.routing == "hard":
+                if expert is None or tuple(expert.shape) != (self.batch,):
+                    raise ValueError(f"session(which=None): run needs expert= of shape ({self.batch},)")
+            elif weights is None or tuple(weights.shape) != (self.batch, eng.E):
+                raise ValueError(f"session(which=None, routing='soft'): run needs weights= of shape "
+                                 f"({self.batch}, {eng.E})")
+        elif expert is not None or weights is not None:
+            raise ValueError("session: expert= / weights= are for a session without a classifier (which=None)")
+        self.x.copy_(x, non_blocking=True)
+        if self.which is None:
+            if self.routing == "hard":
+                self.pred.copy_(expert, non_blocking=True)
+            else:
+                self.wmix.copy_(weights, non_blocking=True)
+        self._step()
+        pred = None if (self.which is None and self.routing == "soft") else self.pred
+        return self.Y, pred, self.logp
+
+    def close(self) -> None:
+        """Retire the session: its graph executable is parked (utils/profiling.py) and ``run`` refuses."""
+        if self._step is not None:
+            self._step.close()
+            self._step = None
