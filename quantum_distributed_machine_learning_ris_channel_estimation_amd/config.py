@@ -105,6 +105,12 @@ class RunnerConfig:
     qsc_post_quant_levels: int = 0
     qsc_post_quant_range: float = 2.0
     qsc_post_quant_weight: float = 0.0
+    # quantum natural gradient (ops/qng.py, off by default; train-qsc on either qsc_step, any measurement mode, world
+    # size 1 only): before AdamW sees it, every (layer, RY | RZ) block of the quantum layer's gradient is solved
+    # against (g + qsc_qng_lambda I), g the block-diagonal Fubini-Study metric of the noiseless circuit at the clean
+    # master weights, averaged over the step's samples.  The QOC pruner still accounts the raw gradient.
+    qsc_qng: bool = False
+    qsc_qng_lambda: float = 0.01
 
     def update_from_dict(self, d: Dict[str, Any]) -> "RunnerConfig":
         names = {f.name: f for f in dataclasses.fields(self)}

@@ -108,6 +108,8 @@ class QuantumLayer(nn.Module):
         self.trajectories = trajectories
         self.shot_seed = 0
         self._shot_calls = 0
+        self.keep_input = False   # True: every forward leaves its angles, detached, in last_input (ops/qng.py reads them)
+        self.last_input = None
         self.weights = nn.Parameter(init_weights_(torch.empty(n_layers, n_qubits, 2)))
 
     def manual_shot_seed(self, seed: int) -> None:
@@ -117,6 +119,8 @@ class QuantumLayer(nn.Module):
 
     def forward(self, x: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         w = self.weights if weights is None else weights
+        if self.keep_input:
+            self.last_input = x.detach()
         kw = {} if self.diff_method == "adjoint" else {"diff_method": self.diff_method, "shift_mask": self.shift_mask}
         if self.noise is not None:
             kw.update(noise=self.noise, trajectories=int(self.trajectories))

@@ -890,6 +890,33 @@ class ClassifierStep:
             from ..ops.sc import SCStepHIP   # (any batch size: the kernels take B per call)
             self.hip = SCStepHIP(model, space, batch_total or 0)
         self.is_sc = isinstance(model, SC_P128)
+        self.qng = None
+        self._batch_total = batch_total
+        self._hip_angles = False   # the last step ran the fused kernels: its angles are QSCStepHIP.angles
+
+    def set_qng(self, qng) -> None:
+        """Attach a ``QNGPreconditioner`` (ops/qng.py): the step keeps its embedding angles, and ``precondition``
+        turns the quantum layer's gradient into the natural gradient."""
+        if not (isinstance(self.model, QSC_P128) and self.model.use_quantum):
+            raise ValueError("the quantum natural gradient needs a QSC_P128 with its quantum layer")
+        self.qng = qng
+        self.model.qlayer.keep_input = True
+        if self._batch_total:
+            qng.reserve(self._batch_total)
+
+    @property
+    def angles(self) -> Optional[torch.Tensor]:
+        """The embedding angles (rows, n) of the last training step: the fused step's buffer, or the quantum layer's
+        kept input on the module path (``qlayer.keep_input``)."""
+        if self._hip_angles:
+            return self.hip.angles
+        return self.model.qlayer.last_input
+
+    def precondition(self) -> None:
+        """The attached preconditioner on the quantum layer's gradient, in place, at the last step's angles and the
+        clean master weights; on the current stream (captured with the step)."""
+        w = self.model.qlayer.weights
+        self.qng.precondition(w.grad, self.angles, w)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """Inference log-probabilities.  GPU: the HIP kernels (the SC's fused forward; for the QSC the
@@ -954,6 +981,7 @@ class ClassifierStep:
     def __call__(self, x: torch.Tensor, labels: torch.Tensor, slabs=None) -> torch.Tensor:
         """``slabs`` (HIP path): queue the gradient-slab reductions on this ``SlabBatch`` (launched by
         the caller, with accumulate = not writes_grads)."""
+        self._hip_angles = self.hip is not None and not self.is_sc and x.shape[0] == self.hip.B
         if self.hip is not None and (self.is_sc or x.shape[0] == self.hip.B):
             loss = self.hip(x.contiguous(), labels, skip=self.skip, skip_add=self.skip_add,
                             accumulate=not self.writes_grads, slabs=slabs)

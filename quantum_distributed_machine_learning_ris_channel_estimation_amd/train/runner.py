@@ -572,13 +572,27 @@ class Y2HRunner:
         return QOCPruner(model.qlayer.weights.numel(), ratio, int(self.qsc_prune_accum), int(self.qsc_prune_window),
                          seed=self.seed, device=self._context().device)
 
+    def qsc_qng_preconditioner(self, model):
+        """The ``QNGPreconditioner`` of the qsc_qng knobs over the quantum layer (ops/qng.py), or None with
+        qsc_qng = false.  The batch metric is the mean over the step's samples: more than one rank would need a
+        collective, so world size 1 only."""
+        if not self.qsc_qng:
+            return None
+        if self._context().world > 1:
+            raise ValueError("qsc_qng trains at world size 1 only: the batch metric would need a collective")
+        from ..ops.qng import QNGPreconditioner
+        return QNGPreconditioner(model.qlayer.n_qubits, model.qlayer.n_layers, float(self.qsc_qng_lambda),
+                                 device=self._context().device)
+
     def _train_classifier(self, model, kind: str, opt_name: str, wd: float, prune_thr: float,
                           on_epoch, histories: Tuple[List, List, List], extra: Optional[Dict] = None,
-                          module_path: bool = False, hip_kw: Optional[Dict] = None, pruner=None):
+                          module_path: bool = False, hip_kw: Optional[Dict] = None, pruner=None, qng=None):
         """``extra``: small mutable trainer state (e.g. best accuracy) saved in the resume file.  ``module_path``:
         train through the model's own forward and autograd, ungraphed.  ``hip_kw``: the fused step's measured-mode
         arguments (qsc_step=fused).  ``pruner``: a ``QOCPruner`` updated with the quantum layer's raw gradient after
-        every step, before the optimizer's own threshold pruning; its mask is the step's ``shift_mask``."""
+        every step, before the optimizer's own threshold pruning; its mask is the step's ``shift_mask``.  ``qng``: a
+        ``QNGPreconditioner`` applied to the quantum layer's gradient after the pruner has seen it and before the
+        optimizer does."""
         ctx = self._context()
         tr, va = self.device_stores()
         model = model.to(ctx.device)
@@ -597,6 +611,8 @@ class Y2HRunner:
                 hip_kw = dict(hip_kw, shift_mask=pruner.mask)
         cstep = ClassifierStep(model, S) if module_path else ClassifierStep(model, S, space=space, batch_total=S * Bl,
                                                                             hip_kw=hip_kw)
+        if qng is not None:
+            cstep.set_qng(qng)
         skip = cstep.skip if self.nan_guard else None
         buckets = GradBuckets(ctx, {"all": [space.grad] + ([skip] if skip is not None else [])})
         cstep.grad_hook = buckets.launch
@@ -635,6 +651,8 @@ class Y2HRunner:
             buckets.wait()
             if pruner is not None:
                 pruner.update(model.qlayer.weights.grad)
+            if qng is not None:
+                cstep.precondition()
             opt.step(grad_scale=gscale, skip=skip)
 
         graphed = GraphedStep(lambda: run(static_idx), enabled=self._graphs_on() and not module_path)
@@ -757,7 +775,7 @@ class Y2HRunner:
                                                 (self.train_QSC_losses, self.val_QSC_losses, self.val_QSC_accuracies),
                                                 extra=state, module_path=on_chip and not fused,
                                                 hip_kw=dict(knobs, shot_seed=self.seed) if fused else None,
-                                                pruner=pruner)
+                                                pruner=pruner, qng=self.qsc_qng_preconditioner(model))
         return self.qsc_model
 
     def train_SC_P128(self):
