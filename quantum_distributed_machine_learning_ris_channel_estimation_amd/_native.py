@@ -81,14 +81,12 @@ def hipcc() -> Optional[str]:
 # hazard_probe.hip: the one file WITH packed-FP32 instructions (its inline asm demonstrates their hazard; see below)
 # qsim_stream.hip also without the SI load/store optimizer: it pairs the streamed passes' 8-byte LDS accesses into
 # ds_read2_b64 / ds_write2_b64, whose banks wrap every 32 dwords -- 24 % of the reverse pass A's LDS cycles were bank
-# conflicts (profiles/r6_54_qstream_pmc_b.md); single ds_read_b64 bank on 64 (QDML_QSTREAM_LSO=1: the paired build)
-_QS_LSO = [] if os.environ.get("QDML_QSTREAM_LSO") == "1" else ["-Xclang", "-target-feature", "-Xclang", "-load-store-opt"]
-PER_FILE_FLAGS = {"gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "qsim_stream.hip": ["-fno-slp-vectorize"] + _QS_LSO,
+# conflicts (profiles/r6_54_qstream_pmc_b.md); single ds_read_b64 bank on 64.  The MFMA simulators measured level
+# without it (README "Measured in round 6 and not adopted": paired LDS accesses are not what bounds them).
+PER_FILE_FLAGS = {"gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+                  "qsim_stream.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-load-store-opt"],
                   "qsim_mfma.hip": ["-fno-slp-vectorize"], "qsim12_mfma.hip": ["-fno-slp-vectorize"],
                   "hazard_probe.hip": ["-Xclang", "-target-feature", "-Xclang", "+packed-fp32-ops"]}
-# (measurement) more files without the SI load/store optimizer: QDML_NOLSO_FILES="a.hip,b.hip"
-for _f in filter(None, os.environ.get("QDML_NOLSO_FILES", "").split(",")):
-    PER_FILE_FLAGS[_f] = PER_FILE_FLAGS.get(_f, []) + ["-Xclang", "-target-feature", "-Xclang", "-load-store-opt"]
 # No packed-FP32 VALU (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) anywhere else (round 6).  On gfx950 a packed-FP32
 # instruction whose source registers are rewritten by a younger LDS read can -- while another wave on its SIMD is
 # issuing MFMAs -- read the NEW value in its last quarter-wave (lanes 48-63): 44,687 of 2,048,000 probe iterations
@@ -100,6 +98,13 @@ if os.environ.get("QDML_PACKED_F32") == "1":   # (measurement only: the hazard-e
     NO_PACKED_F32 = []
 
 
+def hip_flags() -> List[str]:
+    """The flags every csrc/hip source is compiled with; PER_FILE_FLAGS come on top (scripts/build_ab_lib.sh too)."""
+    flags = [f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast",
+             "-Wno-unused-result", "-I", os.path.join(CSRC, "hip")] + NO_PACKED_F32
+    return flags + os.environ.get("QDML_HIPCC_EXTRA", "").split()   # (tuning sweeps: extra -D defines)
+
+
 def build_hip(force: bool = False, verbose: bool = True, jobs: int = 8) -> str:
     cc = hipcc()
     if cc is None:
@@ -107,9 +112,7 @@ def build_hip(force: bool = False, verbose: bool = True, jobs: int = 8) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     srcs = _sources("hip", ".hip")
     hdrs = _headers("hip")
-    flags = [f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast",
-             "-Wno-unused-result", "-I", os.path.join(CSRC, "hip")] + NO_PACKED_F32
-    flags += os.environ.get("QDML_HIPCC_EXTRA", "").split()   # (tuning sweeps: extra -D defines)
+    flags = hip_flags()
     # a changed flag set (a tuning build, then the default again) rebuilds every object
     stamp = os.path.join(OBJ_DIR, "flags.txt")
     want = " ".join(f for f in flags if not f.startswith("/"))   # (not the include path: the tree moves)
