@@ -159,6 +159,9 @@ class EvalConfig:
     qsc_readout01: float = 0.0
     qsc_readout10: float = 0.0
     qsc_trajectories: int = 1
+    # True: the rates above are evaluated exactly -- the expectation of the noisy device itself, the density matrix of
+    # ops/quantum.py qsim_mixed (n_qubits <= 8), with no shots and no trajectories: needs qsc_shots == 0
+    qsc_noise_exact: bool = False
     # a quantum SC trained with post-measurement normalization (its checkpoint says so): normalize with the statistics
     # of the evaluated chunk itself ("batch": removes a noisy device's per-wire affine distortion, but a prediction
     # then depends on the chunk it is in) or with the running statistics of training ("running")

@@ -394,6 +394,75 @@ QD_API int qd_cpu_sample_z_noisy(const float* probs, const int32_t* amask, const
   return 0;
 }
 
+// ------------------------------------------------------------------------------- exact noisy expectation
+// The oracle of csrc/hip/qsim_mixed.hip (its header states the definition): the density matrix of the circuit under
+// the Pauli channel qsim_noise.hip samples, taken in expectation, gate by gate in complex128.  rho[r, c] is entry
+// r | c << n of a 2n-bit vector: a gate is U on bit q and conj(U) on bit n + q, so the state-vector `apply` runs it.
+namespace {
+// out += coef P rho P for the Pauli string with X mask xm and Z mask zm (Y = both): entry (r, c) takes
+// (-1)^(popc(zm & r) + popc(zm & c)) rho[r ^ xm, c ^ xm] (the phases i, -i of the two sides cancel).
+void pauli_conj_add(const std::vector<cd>& rho, std::vector<cd>& out, double coef, size_t xm, size_t zm, int n) {
+  const size_t D = size_t(1) << n;
+  for (size_t c = 0; c < D; ++c)
+    for (size_t r = 0; r < D; ++r) {
+      const bool neg = (__builtin_popcountll(zm & r) + __builtin_popcountll(zm & c)) & 1;
+      const cd v = rho[(r ^ xm) | ((c ^ xm) << n)];
+      out[r | (c << n)] += neg ? -coef * v : coef * v;
+    }
+}
+
+// rho <- (1 - p) rho + (p / (4^k - 1)) sum over the non-identity Paulis on `wires` (k = 1 or 2 of them).
+void pauli_channel(std::vector<cd>& rho, std::vector<cd>& tmp, double p, const int* wires, int k, int n) {
+  if (p == 0.0) return;
+  const int codes = 1 << (2 * k);
+  for (size_t i = 0; i < rho.size(); ++i) tmp[i] = (1.0 - p) * rho[i];
+  for (int code = 1; code < codes; ++code) {
+    size_t xm = 0, zm = 0;
+    for (int j = 0; j < k; ++j) {   // (code = 4 P_control + P_target: the first wire takes the high digit)
+      const uint32_t pj = (uint32_t)(code >> (2 * (k - 1 - j))) & 3u;
+      xm |= (size_t)pauli_x(pj) << wires[j];
+      zm |= (size_t)pauli_z(pj) << wires[j];
+    }
+    pauli_conj_add(rho, tmp, p / (codes - 1), xm, zm, n);
+  }
+  rho.swap(tmp);
+}
+
+void apply_rho(std::vector<cd>& rho, int type, int q, int c, double angle, int n) {
+  apply(rho, Gate{type, q, c, -1, -1, angle}, false);
+  apply(rho, Gate{type, q + n, c < 0 ? -1 : c + n, -1, -1, type == kRZ ? -angle : angle}, false);
+}
+}  // namespace
+
+// probs (B, 2^n) double: the diagonal of rho behind the last ring, natural basis order, before the readout.
+// thr1 / thr2 (n) uint32: the gate thresholds, p = thr / 2^32.  2 <= n <= 8, L >= 1, 2 n L <= 4096.
+QD_API int qd_cpu_qsim_mixed_probs(const float* x, const float* w, const uint32_t* thr1, const uint32_t* thr2,
+                                   double* probs, int B, int n, int L) {
+  if (n < 2 || n > 8 || L < 1 || 2 * n * L > 4096 || B < 0) return 1;
+  const size_t D = size_t(1) << n;
+#pragma omp parallel for schedule(static)
+  for (int b = 0; b < B; ++b) {
+    std::vector<cd> rho(D * D, cd(0)), tmp(D * D);
+    rho[0] = 1.0;
+    for (int l = 0; l < L; ++l) {
+      for (int q = 0; q < n; ++q) {
+        const int p = (l * n + q) * 2;
+        if (l == 0) apply_rho(rho, kRY, q, -1, (double)x[(size_t)b * n + q], n);
+        apply_rho(rho, kRY, q, -1, (double)w[p], n);
+        apply_rho(rho, kRZ, q, -1, (double)w[p + 1], n);
+        pauli_channel(rho, tmp, (double)thr1[q] / 4294967296.0, &q, 1, n);
+      }
+      for (int q = 0; q < n; ++q) {
+        const int wires[2] = {q, (q + 1) % n};
+        apply_rho(rho, kCNOT, wires[1], wires[0], 0.0, n);
+        pauli_channel(rho, tmp, (double)thr2[q] / 4294967296.0, wires, 2, n);
+      }
+    }
+    for (size_t k = 0; k < D; ++k) probs[(size_t)b * D + k] = rho[k | (k << n)].real();
+  }
+  return 0;
+}
+
 // ------------------------------------------------------------------------------- QOC gradient pruning
 // The host twin of qd_qoc_update (csrc/hip/qoc.hip; the contract is stated at the top of that file), sequentially:
 // bit-identical acc, mask and step.

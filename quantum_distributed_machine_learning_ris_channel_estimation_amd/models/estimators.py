@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.quantum import qsim, init_weights_
+from ..ops.quantum import qsim, qsim_mixed, init_weights_
 
 PILOT_GRID = {128: (16, 8), 256: (16, 16)}  # P128 is the reference grid (R:108); P256 is ours
 
@@ -94,7 +94,11 @@ class QuantumLayer(nn.Module):
     ``noise`` (settable; None or an ``ops.quantum.NoiseModel``) and ``trajectories`` (settable; 1 .. 1024) measure
     the shots on a device with Pauli gate errors and readout error (``qsim(noise=, trajectories=)``); they need
     ``shots``, and gradients stay those of the noiseless circuit unless ``diff_method`` is "on_chip" or
-    "noisy_adjoint" (needs ``noise`` and ``shots``: the adjoint through the error gates the forward sampled)."""
+    "noisy_adjoint" (needs ``noise`` and ``shots``: the adjoint through the error gates the forward sampled).
+
+    ``exact_noise`` (settable; default False): with ``noise`` set and ``shots`` not, the forward is the exact
+    expectation of the noisy device, ``ops.quantum.qsim_mixed`` (n <= 8; its gradient is the exact one), instead of
+    the refusal "noise needs shots"."""
 
     def __init__(self, n_qubits: int, n_layers: int, backend: Optional[str] = None, shots: Optional[int] = None,
                  diff_method: str = "adjoint", noise=None, trajectories: int = 1):
@@ -106,6 +110,7 @@ class QuantumLayer(nn.Module):
         self.shift_mask = None
         self.noise = noise
         self.trajectories = trajectories
+        self.exact_noise = False   # True (with noise and no shots): the exact expectation of the noisy device
         self.shot_seed = 0
         self._shot_calls = 0
         self.keep_input = False   # True: every forward leaves its angles, detached, in last_input (ops/qng.py reads them)
@@ -121,6 +126,8 @@ class QuantumLayer(nn.Module):
         w = self.weights if weights is None else weights
         if self.keep_input:
             self.last_input = x.detach()
+        if self.exact_noise and self.noise is not None and not self.shots:
+            return qsim_mixed(x.float(), w, self.noise, self.backend)
         kw = {} if self.diff_method == "adjoint" else {"diff_method": self.diff_method, "shift_mask": self.shift_mask}
         if self.noise is not None:
             kw.update(noise=self.noise, trajectories=int(self.trajectories))

@@ -27,8 +27,9 @@ from .. import _native as nat
 from .slabsum import SlabBatch
 from ..ops.optim import FlatParamSpace
 from ..knobs import KNOBS
-from ..ops.quantum import (HIP_REG_MAX_QUBITS, HIP_SHOTS_MAX_QUBITS, _hip_shots_limit, counter_add, hip_measured_fwd,
-                           hip_measured_rows, hip_qsim_bwd_slab, resolve_measure, split_counter, stream_sim_ok)
+from ..ops.quantum import (HIP_REG_MAX_QUBITS, HIP_SHOTS_MAX_QUBITS, _hip_shots_limit, _mixed_backend, counter_add,
+                           hip_measured_fwd, hip_measured_rows, hip_qsim_bwd_slab, hip_qsim_mixed_fwd, resolve_measure,
+                           split_counter, stream_sim_ok)
 
 _p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 
@@ -341,25 +342,35 @@ class QSCStepHIP:
     @torch.no_grad()
     def infer(self, x: torch.Tensor, pred: Optional[torch.Tensor] = None,
               logp: Optional[torch.Tensor] = None, shots: int = 0, seed: int = 0, counter=0, noise=None,
-              trajectories: int = 1, valid: Optional[int] = None) -> None:
+              trajectories: int = 1, valid: Optional[int] = None, exact_noise: bool = False) -> None:
         """Inference on the HIP kernels (x.shape[0] == B): preprocess CNN, the circuit with the clean
         master weights (no QuantumNAT noise), then a thread-per-sample head -> log-probabilities (B, C)
         and / or the argmax (B,) int64.  ``shots`` > 0: the circuit's <Z_i> are finite-shot estimates
         (csrc/hip/qsim_shots.hip's fused kernel on the angles at n <= 12, the streamed simulator's finite-shot
         forward, csrc/hip/qsim_stream_shots.hip, at n = 13..16; ``seed`` / ``counter`` as in
         ops.quantum.qsim).  ``noise`` / ``trajectories`` (with ``shots``): the shots are measured under that
-        ``NoiseModel`` (csrc/hip/qsim_noise.hip).  ``valid`` (a model with ``postmeas``; default B): the real rows
+        ``NoiseModel`` (csrc/hip/qsim_noise.hip).  ``exact_noise`` (with ``noise`` and no ``shots``): the <Z_i> are
+        the exact expectation of that noisy device, the density matrix of csrc/hip/qsim_mixed.hip on the angles
+        (n <= 8); head and post-measurement path as ever.  ``valid`` (a model with ``postmeas``; default B): the real rows
         of a padded batch -- the batch statistics of the post-measurement normalization go over those only
         (csrc/hip/qsc_postmeas.hip qd_qsc_infer_head_pm, with the module's ``stats``)."""
         m = self.m
         B, n, L = self.B, self.n, self.L
         assert x.shape[0] == B and x.is_contiguous() and self.impl == "mfma"
         st = nat.stream_ptr(x.device)
-        self._fwd_mfma(x, self.space.flat, st)
         w = m.qlayer.weights.detach().contiguous()
-        if noise is not None and not shots:
+        if exact_noise:   # (refused before the first launch)
+            if shots:
+                raise ValueError("exact_noise computes the expectation of the noisy device itself: it takes no shots")
+            if noise is None:
+                raise ValueError("exact_noise needs noise=NoiseModel(...)")
+            _mixed_backend(self.angles, w, noise, "hip")
+        self._fwd_mfma(x, self.space.flat, st)
+        if exact_noise:
+            hip_qsim_mixed_fwd(self.angles, w, self.E, None, noise)
+        elif noise is not None and not shots:
             raise ValueError("noise needs shots")
-        if shots:
+        elif shots:
             mode = resolve_measure("adjoint", shots, noise, trajectories if noise is not None else 1, None, n, L,
                                    "hip", x.device)
             hip_measured_fwd(self.angles, w, self.E, mode, int(seed), *split_counter(counter, x.device))

@@ -44,6 +44,11 @@ fp64 on ``cpu``.
 
 The measurement arguments of all of these are validated in one place, ``resolve_measure``, into a ``MeasureMode``;
 ``qsim`` and the fused step (ops/qsc.py) select their kernels from it through ``hip_measured_fwd`` / ``hip_measured_rows``.
+
+Exact noisy expectation (``qsim_mixed``, ``qsim_mixed_probs``, ``mixed_rows``; functions of their own, ``qsim`` still
+refuses noise without shots): what the noisy modes above estimate -- the density matrix of the circuit under the same
+Pauli channel taken in expectation, then the readout's affine map; no shots, no trajectories;
+csrc/hip/qsim_mixed.hip (n <= 8) on ``hip``, the complex128 oracle of csrc/cpu/qsim_cpu.cpp on ``cpu``.
 """
 from __future__ import annotations
 
@@ -1164,6 +1169,173 @@ def qsim(x: torch.Tensor, w: torch.Tensor, backend: Optional[str] = None, shots:
     if w.dim() == 4:  # host backends: run per group
         return torch.cat([qsim(xc, w[g], be) for g, xc in enumerate(x.chunk(w.shape[0]))], dim=0)
     return _QSimCPU.apply(x, w) if be == "cpu" else qsim_torch(x, w)
+
+
+# ----------------------------------------------------------------------------- exact noisy expectation
+MIXED_MAX_QUBITS = 8             # csrc/hip/qsim_mixed.hip: rho in LDS to 7 qubits, in a workspace slot at 8
+MIXED_ROWS_BYTES = 32 << 20      # mixed_rows: the shifted circuits' extra rows (x, w, E) of one chunk of parameters
+
+
+def _mixed_backend(x: torch.Tensor, w: torch.Tensor, noise, backend: Optional[str]) -> str:
+    """The refusals of the density-matrix functions, before any launch; returns the backend."""
+    _check_shapes(x, w)
+    if not isinstance(noise, NoiseModel):
+        raise ValueError(f"the density-matrix simulator needs noise=NoiseModel(...) (all-zero rates are allowed), got "
+                         f"{type(noise).__name__}")
+    n, L = x.shape[1], w.shape[-3]
+    be = backend if backend not in (None, "auto") else default_backend(x.device)
+    if be == "torch":
+        raise ValueError("the torch backend has no density-matrix simulator; use hip or cpu")
+    if be not in ("hip", "cpu"):
+        raise ValueError(f"unknown backend {be!r}")
+    if n > MIXED_MAX_QUBITS:   # (the host oracle keeps the kernel's range: one contract)
+        raise NotImplementedError(f"the density-matrix simulator supports n <= {MIXED_MAX_QUBITS} qubits "
+                                  f"(rho has 4^n entries), got {n}")
+    if 2 * n * L > MAX_NOISE_SITES:
+        raise ValueError(f"the density-matrix simulator supports 2 n L <= {MAX_NOISE_SITES} error sites, got n={n} L={L}")
+    want = "cuda" if be == "hip" else "cpu"
+    if x.device.type != want or w.device.type != want:
+        raise ValueError(f"the {be} density-matrix simulator needs {want.upper()} tensors, got x on {x.device} and w on "
+                         f"{w.device}")
+    return be
+
+
+def mixed_force_grid(grid: int) -> None:
+    """Tests and timing: csrc/hip/qsim_mixed.hip launches at most ``grid`` workgroups from now on; 0 hands the choice
+    back to the launcher."""
+    nat.check(nat.fn(nat.hip_lib(), "qd_qsim_mixed_force_grid", [_i])(int(grid)), "qd_qsim_mixed_force_grid")
+
+
+def hip_qsim_mixed_fwd(x: torch.Tensor, w: torch.Tensor, E: torch.Tensor, probs: Optional[torch.Tensor],
+                       noise: NoiseModel, wgroup: int = 0) -> None:
+    """Raw launcher of csrc/hip/qsim_mixed.hip (2 <= n <= 8): E (B, n) fp32, the exact expectation of the device
+    under ``noise``; probs (nullable; B, 2^n) fp32, the diagonal of rho before the readout."""
+    lib = nat.hip_lib()
+    B, n = x.shape
+    thr1, thr2, thr_ro = noise.thresholds(n, x.device)
+    nbytes = nat.fn(lib, "qd_qsim_mixed_workspace", [_i, _i], ctypes.c_longlong)(n, B)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    f = nat.fn(lib, "qd_qsim_mixed_fwd", [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p])
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(thr1), nat.ptr(thr2), nat.ptr(thr_ro), nat.ptr(E), _opt(probs), B, n,
+                w.shape[-3], wgroup, _opt(ws), nat.stream_ptr(x.device)), "qd_qsim_mixed_fwd")
+
+
+def mixed_readout(noise: NoiseModel, n: int):
+    """(c, d) (n) fp64 of the readout's affine map E_i = c_i <Z_i> + d_i: c_i = 1 - (thr01_i + thr10_i) / 65536,
+    d_i = (thr10_i - thr01_i) / 65536 from the model's 16-bit thresholds (as ``noisy_adjoint_rows``)."""
+    thr_ro = torch.from_numpy(noise.thresholds_host(n)[2].astype("int64"))
+    return (1.0 - (thr_ro[:, 0] + thr_ro[:, 1]).double() / 65536.0,
+            (thr_ro[:, 1] - thr_ro[:, 0]).double() / 65536.0)
+
+
+def _mixed_probs_cpu(x: torch.Tensor, w: torch.Tensor, noise: NoiseModel) -> torch.Tensor:
+    B, n = x.shape
+    if w.dim() == 4:   # the host oracle runs per group
+        return torch.cat([_mixed_probs_cpu(xc, w[g], noise) for g, xc in enumerate(x.chunk(w.shape[0]))], dim=0)
+    thr1, thr2, _ = noise.thresholds(n, "cpu")
+    probs = torch.empty(B, 1 << n, dtype=torch.float64)
+    f = nat.fn(nat.cpu_lib(), "qd_cpu_qsim_mixed_probs", [_p, _p, _p, _p, _p, _i, _i, _i])
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(thr1), nat.ptr(thr2), nat.ptr(probs), B, n, w.shape[0]),
+              "qd_cpu_qsim_mixed_probs")
+    return probs
+
+
+@torch.no_grad()
+def _mixed_fwd(x: torch.Tensor, w: torch.Tensor, noise: NoiseModel, be: str, want_probs: bool = False):
+    """E (B, n), or the probabilities (B, 2^n): fp32 on ``hip``, fp64 on ``cpu``; x, w checked, fp32, contiguous."""
+    B, n = x.shape
+    if be == "hip":
+        E = torch.empty(B, n, device=x.device, dtype=torch.float32)
+        probs = torch.empty(B, 1 << n, device=x.device, dtype=torch.float32) if want_probs else None
+        if B > 0:
+            hip_qsim_mixed_fwd(x, w, E, probs, noise, wgroup_of(x, w))
+        return probs if want_probs else E
+    probs = _mixed_probs_cpu(x, w, noise)
+    if want_probs:
+        return probs
+    c, d = mixed_readout(noise, n)
+    return c * (probs @ z_signs(n, dtype=torch.float64)) + d
+
+
+def qsim_mixed_probs(x: torch.Tensor, w: torch.Tensor, noise: NoiseModel, backend: Optional[str] = None) -> torch.Tensor:
+    """Outcome probabilities (B, 2^n) of the noisy device before the readout error, natural basis order: the diagonal
+    of the density matrix ``qsim_mixed`` evolves.  fp32 on ``hip``, fp64 on ``cpu``.  No autograd."""
+    be = _mixed_backend(x, w, noise, backend)
+    return _mixed_fwd(x.detach().float().contiguous(), w.detach().float().contiguous(), noise, be, want_probs=True)
+
+
+def _mixed_rows(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, noise: NoiseModel, be: str) -> torch.Tensor:
+    B, n = x.shape
+    L = w.shape[-3]
+    P = 2 * n * L
+    wg = w.reshape(-1, P)                       # (G0, P): the call's own weight groups
+    G0 = wg.shape[0]
+    per = 2 * (B * 2 * n + G0 * P) * 4          # bytes of one parameter's two circuits: x and E rows, weights
+    step = max(1, min(P, MIXED_ROWS_BYTES // per))
+    g = gE.double() if be == "cpu" else gE      # (E carries the readout's c; its d cancels in the difference)
+    G = torch.empty(B, P, device=x.device, dtype=torch.float32)
+    shift = torch.tensor([0.5 * math.pi, -0.5 * math.pi], device=x.device)
+    for p0 in range(0, P, step):
+        k = min(step, P - p0)
+        ws = wg.repeat(k, 2, 1, 1)              # (k, 2, G0, P): parameter p0 + i shifted by +-pi/2
+        idx = torch.arange(k, device=x.device)
+        ws[idx, :, :, p0 + idx] += shift[None, :, None]
+        E = _mixed_fwd(x.repeat(2 * k, 1), ws.view(2 * k * G0, L, n, 2), noise, be).view(k, 2, B, n)
+        G[:, p0:p0 + k] = ((E[:, 0] - E[:, 1]) * g).sum(-1).mul_(0.5).t()
+    return G
+
+
+@torch.no_grad()
+def mixed_rows(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, noise: NoiseModel, backend: Optional[str] = None,
+               need_dx: bool = True) -> torch.Tensor:
+    """Per-sample gradients G (B, 2nL) fp32 of sum(gE * qsim_mixed(x, w, noise)), in ``pshift_rows``'s layout: column
+    p = (l n + q) 2 + k is w[l, q, k]'s; dx = G[:, 0:2n:2]; dw = G summed over the samples.  The +-pi/2 shift rule,
+    exact here (the channel is linear and every generator has two eigenvalues): two forward evaluations per parameter,
+    launched over the shifted weights as grouped ``w``, in chunks of parameters whose extra rows stay under
+    ``MIXED_ROWS_BYTES``.  ``need_dx`` is accepted for symmetry with ``pshift_rows``: every column is computed."""
+    be = _mixed_backend(x, w, noise, backend)
+    B, n = x.shape
+    if tuple(gE.shape) != (B, n):
+        raise ValueError(f"gE must be ({B}, {n}), got {tuple(gE.shape)}")
+    if gE.device != x.device:
+        raise ValueError(f"gE must be on {x.device}, got {gE.device}")
+    return _mixed_rows(x.detach().float().contiguous(), w.detach().float().contiguous(),
+                       gE.detach().float().contiguous(), noise, be)
+
+
+class _QSimMixed(torch.autograd.Function):
+    """Forward: the exact noisy expectation.  Backward: its exact gradient, ``mixed_rows``."""
+
+    @staticmethod
+    def forward(ctx, x, w, noise, be):
+        x = x.detach().float().contiguous()
+        w = w.detach().float().contiguous()
+        ctx.save_for_backward(x, w)
+        ctx.args = (noise, be)
+        return _mixed_fwd(x, w, noise, be).float()
+
+    @staticmethod
+    def backward(ctx, gE):
+        x, w = ctx.saved_tensors
+        noise, be = ctx.args
+        G = _mixed_rows(x, w, gE.detach().float().contiguous(), noise, be)
+        return _rows_to_grads(G, x, w, be) + (None, None)
+
+
+def qsim_mixed(x: torch.Tensor, w: torch.Tensor, noise: NoiseModel, backend: Optional[str] = None) -> torch.Tensor:
+    """<Z_i> (B, n) fp32 of the QSC circuit on the noisy device itself: the expectation that
+    ``qsim(x, w, shots=, noise=, trajectories=)`` estimates, with no Monte-Carlo error -- the density matrix evolved
+    through the circuit with, in expectation, the Pauli channel the sampling kernels draw from (after wire q's fused
+    RZ.RY a uniformly drawn X / Y / Z with probability thr1[q] / 2^32, after every CNOT with control q a uniformly
+    drawn non-identity two-qubit Pauli with probability thr2[q] / 2^32), then the readout's affine map
+    (``mixed_readout``).  The rates are the model's integer thresholds, so a sampler's mean converges to exactly this.
+
+    2 <= n <= 8 (rho has 4^n entries) and 2 n L <= 4096 on both backends: csrc/hip/qsim_mixed.hip on ``hip``, the
+    complex128 gate-by-gate oracle of csrc/cpu/qsim_cpu.cpp on ``cpu``; ``torch`` has none.  ``w`` may be grouped as
+    for ``qsim``.  An all-zero ``NoiseModel`` gives the noiseless expectation.  Differentiable in x and w: the
+    backward is ``mixed_rows`` (two forward evaluations per parameter; there is no dedicated adjoint kernel)."""
+    be = _mixed_backend(x, w, noise, backend)
+    return _QSimMixed.apply(x, w, noise, be)
 
 
 def init_weights_(w: torch.Tensor, generator: Optional[torch.Generator] = None) -> torch.Tensor:

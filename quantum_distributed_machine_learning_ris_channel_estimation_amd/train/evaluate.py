@@ -107,12 +107,16 @@ class model_val:
         ck.load_model_state_dict(model, filepath, fallback_key, map_location=self.device)
 
     def qsc_noise_model(self):
-        """The ``NoiseModel`` of the qsc_noise_* / qsc_readout* knobs (None: all rates zero); it needs qsc_shots."""
+        """The ``NoiseModel`` of the qsc_noise_* / qsc_readout* knobs (None: all rates zero); it needs qsc_shots, or
+        qsc_noise_exact (the exact channel, which takes no shots)."""
         rates = (float(self.qsc_noise_p1), float(self.qsc_noise_p2), float(self.qsc_readout01),
                  float(self.qsc_readout10))
+        exact = bool(getattr(self, "qsc_noise_exact", False))
+        if exact and int(self.qsc_shots) > 0:
+            raise ValueError("qsc_noise_exact evaluates the noisy device's expectation itself: it needs qsc_shots == 0")
         if not any(rates):
             return None
-        if int(self.qsc_shots) <= 0:
+        if int(self.qsc_shots) <= 0 and not exact:
             raise ValueError("qsc_noise_* / qsc_readout* need qsc_shots > 0: the noise model is sampled per shot")
         if self._qsc_noise is None or self._qsc_noise[0] != rates:
             from ..ops.quantum import NoiseModel
@@ -222,17 +226,27 @@ class model_val:
                 continue
             # qsc_shots > 0: the quantum SC's circuit is measured with that many shots per sample (seeded by cfg.seed)
             shots = int(self.qsc_shots) if tag == "quantum" and getattr(clf, "use_quantum", False) else 0
-            noise = self.qsc_noise_model() if shots else None
-            traj = int(self.qsc_trajectories) if noise is not None else 1
+            # qsc_noise_exact: the rates act through the exact channel (ops/quantum.py qsim_mixed), without shots
+            exact = (bool(self.qsc_noise_exact) and tag == "quantum" and getattr(clf, "use_quantum", False)
+                     and self.qsc_noise_model() is not None)
+            noise = self.qsc_noise_model() if shots or exact else None
+            traj = int(self.qsc_trajectories) if noise is not None and not exact else 1
             if eng is not None and (eng.sc if tag == "classical" else eng.qsc) is not None:
                 # the HIP kernels: classifier, experts, routed FC (train/infer.py)
-                pred = (eng.classify(x, tag, shots=shots, seed=self.seed, noise=noise, trajectories=traj,
-                                     return_logp=soft) if shots else eng.classify(x, tag, return_logp=soft))
+                if exact:
+                    pred = eng.classify(x, tag, noise=noise, exact_noise=True, return_logp=soft)
+                else:
+                    pred = (eng.classify(x, tag, shots=shots, seed=self.seed, noise=noise, trajectories=traj,
+                                         return_logp=soft) if shots else eng.classify(x, tag, return_logp=soft))
                 pred, logp = pred if soft else (pred, None)
             else:   # (CPU, or the classical-fallback QSC ablation: torch)
+                if exact:
+                    ql = clf.qlayer
+                    plain = (ql.shots, ql.noise, ql.exact_noise)
+                    ql.shots, ql.noise, ql.exact_noise = None, noise, True
                 if shots:
                     ql = clf.qlayer
-                    exact = (ql.shots, ql.shot_seed, ql._shot_calls, ql.noise, ql.trajectories)
+                    saved_ql = (ql.shots, ql.shot_seed, ql._shot_calls, ql.noise, ql.trajectories)
                     ql.shots, ql.noise, ql.trajectories = shots, noise, traj
                     ql.manual_shot_seed(self.seed)
                 try:
@@ -240,7 +254,9 @@ class model_val:
                     pred = logp.argmax(1)
                 finally:
                     if shots:
-                        ql.shots, ql.shot_seed, ql._shot_calls, ql.noise, ql.trajectories = exact
+                        ql.shots, ql.shot_seed, ql._shot_calls, ql.noise, ql.trajectories = saved_ql
+                    if exact:
+                        ql.shots, ql.noise, ql.exact_noise = plain
             saved = None
             if self.bn_adapt:   # (GPU: the HIP training conv forward computes the statistics, no MIOpen)
                 saved = eng.recalibrate_bn(convs, x, pred) if eng is not None else recalibrate_bn(convs, x, pred)
@@ -332,6 +348,7 @@ class model_val:
             "qsc_noise_p1": float(self.qsc_noise_p1), "qsc_noise_p2": float(self.qsc_noise_p2),
             "qsc_readout01": float(self.qsc_readout01), "qsc_readout10": float(self.qsc_readout10),
             "qsc_trajectories": int(self.qsc_trajectories),
+            "qsc_noise_exact": bool(self.qsc_noise_exact),   # (True: the rates through the exact channel, no shots)
         }
         if nmse_lmmse is not None:
             results["NMSE_LMMSE_dB"] = db(nmse_lmmse)

@@ -202,16 +202,25 @@ class HIPInference:
 
     @torch.no_grad()
     def classify(self, x: torch.Tensor, which: str, shots: int = 0, seed: int = 0, noise=None,
-                 trajectories: int = 1, return_logp: bool = False):
+                 trajectories: int = 1, return_logp: bool = False, exact_noise: bool = False):
         """Predicted scenario (N,) int64 of every sample with the classical ("classical") or quantum SC.
         ``return_logp``: ``(pred, logp)`` with the log-posterior (N, n_classes) fp32 of the same launches -- under
         ``shots`` / ``noise`` the one of the measured <Z_i>, exactly what ``pred`` was taken from.
         ``shots`` > 0 ("quantum" only): the circuit is measured with that many shots per sample; the shot
         stream is keyed by ``seed`` and the chunk index (the counter), the sample's row within its chunk.
-        ``noise`` / ``trajectories`` (with ``shots``): measured under that ``ops.quantum.NoiseModel``."""
+        ``noise`` / ``trajectories`` (with ``shots``): measured under that ``ops.quantum.NoiseModel``.
+        ``exact_noise`` ("quantum" only; with ``noise`` and no ``shots``): the exact expectation of that noisy
+        device instead of a sample of it (``ops.quantum.qsim_mixed``; n <= 8), deterministic."""
         if shots and which != "quantum":
             raise ValueError("shots apply to the quantum classifier only")
-        if noise is not None and not shots:
+        if exact_noise:
+            if which != "quantum":
+                raise ValueError("exact_noise applies to the quantum classifier only")
+            if shots:
+                raise ValueError("exact_noise computes the expectation of the noisy device itself: it takes no shots")
+            if noise is None:
+                raise ValueError("exact_noise needs noise=NoiseModel(...)")
+        elif noise is not None and not shots:
             raise ValueError("noise needs shots")
         clf = self.sc if which == "classical" else self.qsc
         assert clf is not None, f"no {which} classifier loaded"
@@ -231,7 +240,7 @@ class HIPInference:
                 lbuf = self.sc.forward(self.xq, self.pred)
             else:
                 self.qsc.infer(self.xq, self.pred, logp=lbuf, shots=shots, seed=seed, counter=lo // self.chunk,
-                               noise=noise, trajectories=trajectories, valid=n)
+                               noise=noise, trajectories=trajectories, valid=n, exact_noise=exact_noise)
             out[lo:lo + n].copy_(self.pred[:n])
             if return_logp:
                 lp[lo:lo + n].copy_(lbuf[:n])
