@@ -89,6 +89,10 @@ class RunnerConfig:
     qsc_readout01: float = 0.0
     qsc_readout10: float = 0.0
     qsc_trajectories: int = 1
+    # qsc_noise_exact: the rates act through the exact channel instead -- the density matrix of ops/quantum.py
+    # qsim_mixed, no shots and no trajectories (qsc_shots == 0, n_qubits <= 8, gate rates <= 0.5), differentiated by
+    # its one-launch adjoint; in the module path or (qsc_step=fused) the fused, graphed step
+    qsc_noise_exact: bool = False
     # qsc_step: where those modes train -- "module" (the default: the path above) or "fused": the fused, graph-captured
     # step (ops/qsc.py QSCStepHIP's measured modes; on a CPU device the module path).  QOC gradient pruning
     # (ops/qoc.py; needs parameter_shift or on_chip, either path): after every qsc_prune_accum steps that measure all

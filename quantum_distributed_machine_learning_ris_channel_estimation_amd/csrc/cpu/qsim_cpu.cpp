@@ -463,6 +463,122 @@ QD_API int qd_cpu_qsim_mixed_probs(const float* x, const float* w, const uint32_
   return 0;
 }
 
+// The host twin of qd_qsim_mixed_adjoint (csrc/hip/qsim_mixed.hip states the method), in complex128 and in the
+// oracle's gate order reversed.  Lam[r, c] is stored like rho; <Lam, rho> = Re sum conj(Lam) rho.
+namespace {
+// A <- a A + k I (x) tr_wires A on the k wires (1 or 2): the site's map D, or with (1 / a, -k / a) its inverse.
+void site_map(std::vector<cd>& A, double a, double k, const int* wires, int nw, int n) {
+  size_t rm = 0;
+  for (int j = 0; j < nw; ++j) rm |= size_t(1) << wires[j];
+  const size_t both = rm | (rm << n);
+  for (size_t base = 0; base < A.size(); ++base) {
+    if (base & both) continue;
+    cd s = 0;
+    for (size_t v = rm;; v = (v - 1) & rm) {   // the block's diagonal: equal row and column bits on the wires
+      s += A[base | v | (v << n)];
+      if (v == 0) break;
+    }
+    for (size_t r = rm;; r = (r - 1) & rm) {
+      for (size_t c = rm;; c = (c - 1) & rm) {
+        cd& e = A[base | r | (c << n)];
+        e = r == c ? a * e + k * s : a * e;
+        if (c == 0) break;
+      }
+      if (r == 0) break;
+    }
+  }
+}
+
+// <Lam, (-i/2) [P_q, rho]> for P = Z (type kRZ) or Y (kRY): the derivative by the rotation's angle.
+double generator_term(const std::vector<cd>& lam, const std::vector<cd>& rho, int type, int q, int n) {
+  const size_t m0 = size_t(1) << q, m1 = size_t(1) << (n + q);
+  double acc = 0;
+  for (size_t base = 0; base < rho.size(); ++base) {
+    if (base & (m0 | m1)) continue;
+    const cd p0 = rho[base], p1 = rho[base | m0], p2 = rho[base | m1], p3 = rho[base | m0 | m1];
+    const cd l0 = lam[base], l1 = lam[base | m0], l2 = lam[base | m1], l3 = lam[base | m0 | m1];
+    if (type == kRZ)
+      acc += (std::conj(l1) * cd(0, 1) * p1 + std::conj(l2) * cd(0, -1) * p2).real();
+    else
+      acc += 0.5 * (std::conj(l1 + l2) * (p0 - p3) - std::conj(l0 - l3) * (p1 + p2)).real();
+  }
+  return acc;
+}
+}  // namespace
+
+// G (B, 2 n L) double: row b the gradient of sum_j gE[b, j] E[b, j], column (l n + q) 2 + k for w[l, q, k].
+// E (nullable; B, n) double: the expectation with the readout.  thr_ro (n, 2).  The ranges of
+// qd_cpu_qsim_mixed_probs; a gate threshold above 2^31 (p > 1/2) is refused.  Nothing is written on a refusal.
+QD_API int qd_cpu_qsim_mixed_adjoint(const float* x, const float* w, const uint32_t* thr1, const uint32_t* thr2,
+                                     const uint32_t* thr_ro, const float* gE, double* G, double* E, int B, int n,
+                                     int L) {
+  if (n < 2 || n > 8 || L < 1 || 2 * n * L > 4096 || B < 0) return 1;
+  if (!x || !w || !thr1 || !thr2 || !thr_ro || !gE || !G) return 1;
+  for (int q = 0; q < n; ++q)
+    if (thr1[q] > 0x80000000u || thr2[q] > 0x80000000u) return 1;
+  const size_t D = size_t(1) << n;
+  const int P = 2 * n * L;
+#pragma omp parallel for schedule(static)
+  for (int b = 0; b < B; ++b) {
+    std::vector<cd> rho(D * D, cd(0)), lam(D * D, cd(0)), tmp(D * D);
+    rho[0] = 1.0;
+    const float* xs = x + (size_t)b * n;
+    for (int l = 0; l < L; ++l) {
+      for (int q = 0; q < n; ++q) {
+        const int p = (l * n + q) * 2;
+        if (l == 0) apply_rho(rho, kRY, q, -1, (double)xs[q], n);
+        apply_rho(rho, kRY, q, -1, (double)w[p], n);
+        apply_rho(rho, kRZ, q, -1, (double)w[p + 1], n);
+        pauli_channel(rho, tmp, (double)thr1[q] / 4294967296.0, &q, 1, n);
+      }
+      for (int q = 0; q < n; ++q) {
+        const int wires[2] = {q, (q + 1) % n};
+        apply_rho(rho, kCNOT, wires[1], wires[0], 0.0, n);
+        pauli_channel(rho, tmp, (double)thr2[q] / 4294967296.0, wires, 2, n);
+      }
+    }
+    std::vector<double> gc(n);
+    for (int j = 0; j < n; ++j) {
+      const double c = 1.0 - ((double)thr_ro[2 * j] + (double)thr_ro[2 * j + 1]) / 65536.0;
+      gc[j] = (double)gE[(size_t)b * n + j] * c;
+      if (E != nullptr) {
+        double S = 0;
+        for (size_t k = 0; k < D; ++k) S += ((k >> j) & 1) ? -rho[k | (k << n)].real() : rho[k | (k << n)].real();
+        E[(size_t)b * n + j] = c * S + ((double)thr_ro[2 * j + 1] - (double)thr_ro[2 * j]) / 65536.0;
+      }
+    }
+    for (size_t k = 0; k < D; ++k) {
+      double v = 0;
+      for (int j = 0; j < n; ++j) v += ((k >> j) & 1) ? -gc[j] : gc[j];
+      lam[k | (k << n)] = v;
+    }
+    for (int l = L - 1; l >= 0; --l) {
+      for (int q = n - 1; q >= 0; --q) {
+        const int wires[2] = {q, (q + 1) % n};
+        const double p2 = (double)thr2[q] / 4294967296.0, a = 1.0 - 16.0 * p2 / 15.0, k = 4.0 * p2 / 15.0;
+        site_map(rho, 1.0 / a, -k / a, wires, 2, n);
+        site_map(lam, a, k, wires, 2, n);
+        apply_rho(rho, kCNOT, wires[1], wires[0], 0.0, n);
+        apply_rho(lam, kCNOT, wires[1], wires[0], 0.0, n);
+      }
+      for (int q = n - 1; q >= 0; --q) {
+        const int p = (l * n + q) * 2;
+        const double p1 = (double)thr1[q] / 4294967296.0, a = 1.0 - 4.0 * p1 / 3.0, k = 2.0 * p1 / 3.0;
+        const double theta = (double)w[p] + (l == 0 ? (double)xs[q] : 0.0), phi = (double)w[p + 1];
+        site_map(rho, 1.0 / a, -k / a, &q, 1, n);
+        site_map(lam, a, k, &q, 1, n);
+        G[(size_t)b * P + p + 1] = generator_term(lam, rho, kRZ, q, n);
+        apply_rho(rho, kRZ, q, -1, -phi, n);
+        apply_rho(lam, kRZ, q, -1, -phi, n);
+        G[(size_t)b * P + p] = generator_term(lam, rho, kRY, q, n);
+        apply_rho(rho, kRY, q, -1, -theta, n);
+        apply_rho(lam, kRY, q, -1, -theta, n);
+      }
+    }
+  }
+  return 0;
+}
+
 // ------------------------------------------------------------------------------- QOC gradient pruning
 // The host twin of qd_qoc_update (csrc/hip/qoc.hip; the contract is stated at the top of that file), sequentially:
 // bit-identical acc, mask and step.

@@ -98,7 +98,9 @@ class QuantumLayer(nn.Module):
 
     ``exact_noise`` (settable; default False): with ``noise`` set and ``shots`` not, the forward is the exact
     expectation of the noisy device, ``ops.quantum.qsim_mixed`` (n <= 8; its gradient is the exact one), instead of
-    the refusal "noise needs shots"."""
+    the refusal "noise needs shots".  ``exact_diff_method`` (settable; "parameter_shift" by default, or "adjoint")
+    is that forward's backward (``qsim_mixed(diff_method=)``): the shift rule over forward launches, or the one-launch
+    adjoint through the channel (gate rates <= 0.5)."""
 
     def __init__(self, n_qubits: int, n_layers: int, backend: Optional[str] = None, shots: Optional[int] = None,
                  diff_method: str = "adjoint", noise=None, trajectories: int = 1):
@@ -111,6 +113,7 @@ class QuantumLayer(nn.Module):
         self.noise = noise
         self.trajectories = trajectories
         self.exact_noise = False   # True (with noise and no shots): the exact expectation of the noisy device
+        self.exact_diff_method = "parameter_shift"   # ... and its backward: the shift rule, or "adjoint" (one launch)
         self.shot_seed = 0
         self._shot_calls = 0
         self.keep_input = False   # True: every forward leaves its angles, detached, in last_input (ops/qng.py reads them)
@@ -127,7 +130,11 @@ class QuantumLayer(nn.Module):
         if self.keep_input:
             self.last_input = x.detach()
         if self.exact_noise and self.noise is not None and not self.shots:
-            return qsim_mixed(x.float(), w, self.noise, self.backend)
+            # the default makes the four-argument call it always made: tests/test_mixed_cpu.py replaces qsim_mixed
+            # with a function of exactly those arguments
+            if self.exact_diff_method == "parameter_shift":
+                return qsim_mixed(x.float(), w, self.noise, self.backend)
+            return qsim_mixed(x.float(), w, self.noise, self.backend, diff_method=self.exact_diff_method)
         kw = {} if self.diff_method == "adjoint" else {"diff_method": self.diff_method, "shift_mask": self.shift_mask}
         if self.noise is not None:
             kw.update(noise=self.noise, trajectories=int(self.trajectories))

@@ -27,9 +27,10 @@ from .. import _native as nat
 from .slabsum import SlabBatch
 from ..ops.optim import FlatParamSpace
 from ..knobs import KNOBS
-from ..ops.quantum import (HIP_REG_MAX_QUBITS, HIP_SHOTS_MAX_QUBITS, _hip_shots_limit, _mixed_backend, counter_add,
-                           hip_measured_fwd, hip_measured_rows, hip_qsim_bwd_slab, hip_qsim_mixed_fwd, resolve_measure,
-                           split_counter, stream_sim_ok)
+from ..ops.quantum import (HIP_REG_MAX_QUBITS, HIP_SHOTS_MAX_QUBITS, MIXED_MAX_QUBITS, NoiseModel,
+                           _check_adjoint_rates, _hip_shots_limit, _mixed_backend, counter_add, hip_measured_fwd,
+                           hip_measured_rows, hip_qsim_bwd_slab, hip_qsim_mixed_adjoint, hip_qsim_mixed_fwd,
+                           mixed_adjoint_workspace, resolve_measure, split_counter, stream_sim_ok)
 
 _p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 
@@ -45,7 +46,7 @@ class QSCStepHIP:
     def __init__(self, model, space: FlatParamSpace, batch_total: int, n_groups: int = 1,
                  grid_fwd: int = 512, grid_bwd: int = 256, impl: str = "mfma", balance_bwd: bool = True,
                  diff_method: str = "adjoint", shots: Optional[int] = None, noise=None, trajectories: int = 1,
-                 shot_seed: int = 0, shift_mask: Optional[torch.Tensor] = None):
+                 shot_seed: int = 0, shift_mask: Optional[torch.Tensor] = None, exact_noise: bool = False):
         """impl: "mfma" (csrc/hip/qsc_mfma.hip: one wave per sample, fp32 MFMA convs; default) or
         "ref" (csrc/hip/qsc.hip: one workgroup per sample, VALU convs).  balance_bwd (mfma): shrink the
         backward's grid below ``grid_bwd`` until every wave takes the same number of samples.
@@ -56,7 +57,12 @@ class QSCStepHIP:
         method's own kernel, its per-sample rows handed to the fused preprocess backward by qd_qsc_rows_to_step
         (csrc/hip/qsc.hip).  The shot streams follow ``shot_ctr`` (a device counter the step owns and advances after
         every backward).  ``shift_mask``: a CUDA uint8 tensor of 2nL entries held by reference (0 = the parameter's
-        shifted circuits do not run and its gradient is exactly 0); a ``QOCPruner``'s ``mask`` fits."""
+        shifted circuits do not run and its gradient is exactly 0); a ``QOCPruner``'s ``mask`` fits.
+
+        ``exact_noise`` (with ``noise``, no ``shots``, ``diff_method="adjoint"``, n <= 8, gate rates <= 0.5): a
+        measured step on the exact expectation of the noisy device -- the forward is the density matrix of
+        csrc/hip/qsim_mixed.hip on the step's angles and (QuantumNAT-grouped) weights, the backward its one-launch
+        adjoint, handed on by qd_qsc_rows_to_step.  Its workspace is allocated here, once; there is no shot counter."""
         self.m = model
         self.space = space
         dev = space.flat.device
@@ -65,7 +71,7 @@ class QSCStepHIP:
         self.n = model.num_qubits
         self.L = model.n_layers
         self.C = model.n_classes
-        self._init_measured(dev, impl, diff_method, shots, noise, trajectories, shot_seed, shift_mask)
+        self._init_measured(dev, impl, diff_method, shots, noise, trajectories, shot_seed, shift_mask, exact_noise)
         pre = model.preprocess
         names = dict(zip(space.names, space.offsets))
         o = [names["preprocess.0.weight"], names["preprocess.0.bias"], names["preprocess.3.weight"],
@@ -153,7 +159,7 @@ class QSCStepHIP:
         else:
             self.qrows = nat.fn(L, "qd_qsim_bwd_grid", [_i, _i])(self.n, batch_total)
             self.qws = None
-        if self.measured and self.diff_method != "adjoint":
+        if self.measured and (self.diff_method != "adjoint" or self.exact_noise):
             self.qrows = -(-batch_total // 64)   # qd_qsc_rows_to_step: one slab row per 64 samples
         self.qslab = torch.empty(self.qrows, 2 * self.n * self.L, **f32)
         self._pre_fwd = nat.fn(L, "qd_qsc_pre_fwd", [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p])
@@ -225,8 +231,13 @@ class QSCStepHIP:
             self.qops8 = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
             self._qb = nat.fn(L, "qd_qsim_mfma8_bwd", [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p])
 
-    def _init_measured(self, dev, impl, diff_method, shots, noise, trajectories, shot_seed, shift_mask) -> None:
+    def _init_measured(self, dev, impl, diff_method, shots, noise, trajectories, shot_seed, shift_mask,
+                       exact_noise=False) -> None:
         n, L, P = self.n, self.L, 2 * self.n * self.L
+        self.exact_noise = bool(exact_noise)
+        if self.exact_noise:
+            self._init_exact_noise(dev, impl, diff_method, shots, noise, shift_mask)
+            return
         self.measured = bool(shots) or diff_method != "adjoint"
         if self.measured and impl != "mfma":
             raise ValueError(f"a measured step (shots / diff_method) needs impl='mfma', got {impl!r}")
@@ -248,6 +259,36 @@ class QSCStepHIP:
         if diff_method != "adjoint":
             self.Grows = torch.empty(self.B, P, device=dev, dtype=torch.float32)   # the method's per-sample rows
             self._rows = nat.fn(nat.hip_lib(), "qd_qsc_rows_to_step", [_p, _p, _p, _p, _i, _i, _i, _p])
+
+    def _init_exact_noise(self, dev, impl, diff_method, shots, noise, shift_mask) -> None:
+        """The measured step on the exact noisy expectation: refusals, then its rows and its workspace.  As for every
+        measured mode, the constructor still sets up the noiseless simulator's launchers and buffers (a few MB at
+        n <= 8): ``infer`` without ``exact_noise`` runs on them."""
+        n, L, P = self.n, self.L, 2 * self.n * self.L
+        if shots:
+            raise ValueError("exact_noise computes the expectation of the noisy device itself: it takes no shots")
+        if diff_method != "adjoint":
+            raise ValueError(f"exact_noise differentiates by the density-matrix adjoint: diff_method must be "
+                             f"'adjoint', got {diff_method!r}")
+        if not isinstance(noise, NoiseModel):
+            raise ValueError("exact_noise needs noise=NoiseModel(...)")
+        if shift_mask is not None:
+            raise ValueError("exact_noise takes no shift_mask (pruning applies to the shift methods)")
+        if impl != "mfma":
+            raise ValueError(f"a measured step (shots / diff_method) needs impl='mfma', got {impl!r}")
+        if n > MIXED_MAX_QUBITS:
+            raise ValueError(f"exact_noise supports n <= {MIXED_MAX_QUBITS} qubits (rho has 4^n entries), got {n}")
+        if P > 256:
+            raise ValueError(f"a measured step supports 2 n L <= 256 (the fused backward's slab width), got n={n} L={L}")
+        _check_adjoint_rates(noise, n)
+        self.measured = True
+        self.mode = resolve_measure("adjoint", None, None, 1, None, n, L, "hip", dev, mask_shape=False)
+        self.diff_method, self.noise, self.trajectories, self.shots = "adjoint", noise, 1, None
+        self.shot_seed, self.shift_mask = 0, None
+        noise.thresholds(n, dev)   # (uploaded now: a captured step copies nothing)
+        self.Grows = torch.empty(self.B, P, device=dev, dtype=torch.float32)
+        self._rows = nat.fn(nat.hip_lib(), "qd_qsc_rows_to_step", [_p, _p, _p, _p, _i, _i, _i, _p])
+        self.mixed_ws = mixed_adjoint_workspace(n, self.B, dev)   # rho and Lambda (n = 7, 8); the forward's rho fits
 
     def quantum_weights(self) -> torch.Tensor:
         """Master weights, or (training + QuantumNAT) G per-stream noisy copies drawn in-kernel
@@ -318,7 +359,9 @@ class QSCStepHIP:
         extra = (nat.ptr(self.qws) if self.qws is not None else None,
                  nat.ptr(self.psave) if self.psave is not None else None) if self.big else \
             (nat.ptr(self.psave) if self.psave is not None else None,)
-        if self.measured and self.shots:
+        if self.exact_noise:
+            hip_qsim_mixed_fwd(self.angles, w, self.E, None, self.noise, wgroup, ws=self.mixed_ws)
+        elif self.measured and self.shots:
             hip_measured_fwd(self.angles, w, self.E, self.mode, self.shot_seed, 0, nat.ptr(self.shot_ctr), wgroup)
         elif self.mfma:
             nat.check(self._mfwd(nat.ptr(self.angles), nat.ptr(w), nat.ptr(self.qops), nat.ptr(self.E), B, L, wgroup,
@@ -367,7 +410,8 @@ class QSCStepHIP:
             _mixed_backend(self.angles, w, noise, "hip")
         self._fwd_mfma(x, self.space.flat, st)
         if exact_noise:
-            hip_qsim_mixed_fwd(self.angles, w, self.E, None, noise)
+            # (an exact-noise step's own workspace, sized for this batch, serves: nothing is allocated)
+            hip_qsim_mixed_fwd(self.angles, w, self.E, None, noise, ws=getattr(self, "mixed_ws", None))
         elif noise is not None and not shots:
             raise ValueError("noise needs shots")
         elif shots:
@@ -441,13 +485,18 @@ class QSCStepHIP:
                                   self.wl_bs, st), "qsc_outer_partial")
             nat.check(self._ssum(nat.ptr(self.wlslab), nat.ptr(self.gwl), 1, self.wlslab.shape[0], self.n * F,
                                  int(accumulate), st), "qsc_wl_slab_sum")
-        if self.measured:   # (the backward re-read the counter the forward read: advance it only now)
-            counter_add(self.shot_ctr, 1)
+        if self.measured and not self.exact_noise:   # (the exact channel draws nothing: it has no counter)
+            counter_add(self.shot_ctr, 1)   # (the backward re-read the counter the forward read: advance it only now)
         return self.loss
 
     def _measured_backward(self, w, wgroup: int, st) -> torch.Tensor:
         """The measured modes' quantum backward: writes ``dang`` and returns the weight-gradient slab (rows, 2nL)
         the fused preprocess backward reduces."""
+        if self.exact_noise:   # the adjoint through the channel, one launch
+            hip_qsim_mixed_adjoint(self.angles, w, self.dE, self.Grows, None, self.noise, wgroup, ws=self.mixed_ws)
+            nat.check(self._rows(nat.ptr(self.Grows), None, nat.ptr(self.dang), nat.ptr(self.qslab), self.B, self.n,
+                                 self.L, st), "qsc_rows_to_step")
+            return self.qslab
         if self.diff_method == "adjoint":   # straight-through: the exact adjoint of the noiseless circuit
             return hip_qsim_bwd_slab(self.angles, w, self.dE, self.dang)
         hip_measured_rows(self.angles, w, self.dE, self.Grows, self.mode, self.shift_mask, self.shot_seed, 0,

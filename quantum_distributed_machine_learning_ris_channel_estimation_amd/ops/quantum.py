@@ -48,7 +48,9 @@ The measurement arguments of all of these are validated in one place, ``resolve_
 Exact noisy expectation (``qsim_mixed``, ``qsim_mixed_probs``, ``mixed_rows``; functions of their own, ``qsim`` still
 refuses noise without shots): what the noisy modes above estimate -- the density matrix of the circuit under the same
 Pauli channel taken in expectation, then the readout's affine map; no shots, no trajectories;
-csrc/hip/qsim_mixed.hip (n <= 8) on ``hip``, the complex128 oracle of csrc/cpu/qsim_cpu.cpp on ``cpu``.
+csrc/hip/qsim_mixed.hip (n <= 8) on ``hip``, the complex128 oracle of csrc/cpu/qsim_cpu.cpp on ``cpu``.  Its gradient
+is the shift rule over forward launches (``mixed_rows``) or, with ``diff_method="adjoint"``, one reverse-mode launch
+(``mixed_adjoint_rows``; gate rates <= 0.5).
 """
 from __future__ import annotations
 
@@ -1207,14 +1209,18 @@ def mixed_force_grid(grid: int) -> None:
 
 
 def hip_qsim_mixed_fwd(x: torch.Tensor, w: torch.Tensor, E: torch.Tensor, probs: Optional[torch.Tensor],
-                       noise: NoiseModel, wgroup: int = 0) -> None:
+                       noise: NoiseModel, wgroup: int = 0, ws: Optional[torch.Tensor] = None) -> None:
     """Raw launcher of csrc/hip/qsim_mixed.hip (2 <= n <= 8): E (B, n) fp32, the exact expectation of the device
-    under ``noise``; probs (nullable; B, 2^n) fp32, the diagonal of rho before the readout."""
+    under ``noise``; probs (nullable; B, 2^n) fp32, the diagonal of rho before the readout.  ``ws``: a workspace of at
+    least qd_qsim_mixed_workspace(n, B) bytes to use instead of allocating one (n = 8)."""
     lib = nat.hip_lib()
     B, n = x.shape
     thr1, thr2, thr_ro = noise.thresholds(n, x.device)
     nbytes = nat.fn(lib, "qd_qsim_mixed_workspace", [_i, _i], ctypes.c_longlong)(n, B)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    if ws is not None and ws.numel() * ws.element_size() < nbytes:
+        raise ValueError(f"the workspace holds {ws.numel() * ws.element_size()} bytes, the launch needs {nbytes}")
+    if ws is None and nbytes:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     f = nat.fn(lib, "qd_qsim_mixed_fwd", [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p])
     nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(thr1), nat.ptr(thr2), nat.ptr(thr_ro), nat.ptr(E), _opt(probs), B, n,
                 w.shape[-3], wgroup, _opt(ws), nat.stream_ptr(x.device)), "qd_qsim_mixed_fwd")
@@ -1303,26 +1309,112 @@ def mixed_rows(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, noise: NoiseM
                        gE.detach().float().contiguous(), noise, be)
 
 
+MIXED_DIFF_METHODS = ("parameter_shift", "adjoint")
+MIXED_ADJOINT_MAX_THR = 1 << 31   # p <= 1/2: the adjoint inverts the sites, and 1 / (1 - 4p/3) grows without bound
+
+
+def _check_adjoint_rates(noise: NoiseModel, n: int) -> None:
+    """The adjoint's limit, on the integer thresholds the kernels use."""
+    thr1, thr2, _ = noise.thresholds_host(n)
+    if int(thr1.max()) > MIXED_ADJOINT_MAX_THR or int(thr2.max()) > MIXED_ADJOINT_MAX_THR:
+        raise ValueError("the density-matrix adjoint undoes every error site and needs p1, p2 <= 0.5 on every wire "
+                         f"(got p1 up to {float(thr1.max()) / 2 ** 32:.4f}, p2 up to {float(thr2.max()) / 2 ** 32:.4f});"
+                         ' use diff_method="parameter_shift"')
+
+
+def mixed_adjoint_workspace(n: int, B: int, device) -> Optional[torch.Tensor]:
+    """The workspace of ``hip_qsim_mixed_adjoint`` for a batch of B (n = 7, 8: rho and Lambda of every workgroup), or
+    None where it needs none."""
+    nbytes = nat.fn(nat.hip_lib(), "qd_qsim_mixed_adjoint_workspace", [_i, _i], ctypes.c_longlong)(n, B)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
+def hip_qsim_mixed_adjoint(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, G: torch.Tensor,
+                           E: Optional[torch.Tensor], noise: NoiseModel, wgroup: int = 0,
+                           ws: Optional[torch.Tensor] = None) -> None:
+    """Raw launcher of csrc/hip/qsim_mixed.hip's adjoint (2 <= n <= 8, rates <= 0.5): G (B, 2nL) fp32, the gradient
+    rows of sum(gE * E) in ``pshift_rows``'s layout, in one launch; E (nullable; B, n) ``hip_qsim_mixed_fwd``'s, bit
+    for bit.  ``ws``: ``mixed_adjoint_workspace(n, B, device)``, allocated here when not given."""
+    B, n = x.shape
+    _check_adjoint_rates(noise, n)
+    thr1, thr2, thr_ro = noise.thresholds(n, x.device)
+    if ws is None:
+        ws = mixed_adjoint_workspace(n, B, x.device)
+    else:
+        need = nat.fn(nat.hip_lib(), "qd_qsim_mixed_adjoint_workspace", [_i, _i], ctypes.c_longlong)(n, B)
+        if ws.numel() * ws.element_size() < need:
+            raise ValueError(f"the workspace holds {ws.numel() * ws.element_size()} bytes, the launch needs {need}")
+    f = nat.fn(nat.hip_lib(), "qd_qsim_mixed_adjoint", [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p])
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(thr1), nat.ptr(thr2), nat.ptr(thr_ro), nat.ptr(gE), nat.ptr(G), _opt(E),
+                B, n, w.shape[-3], wgroup, _opt(ws), nat.stream_ptr(x.device)), "qd_qsim_mixed_adjoint")
+
+
+def _mixed_adjoint_cpu(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, noise: NoiseModel) -> torch.Tensor:
+    """G (B, 2nL) fp64 of the complex128 host twin (csrc/cpu/qsim_cpu.cpp qd_cpu_qsim_mixed_adjoint)."""
+    B, n = x.shape
+    if w.dim() == 4:   # the host twin runs per group
+        return torch.cat([_mixed_adjoint_cpu(xc, w[g], gc, noise)
+                          for g, (xc, gc) in enumerate(zip(x.chunk(w.shape[0]), gE.chunk(w.shape[0])))], dim=0)
+    thr1, thr2, thr_ro = noise.thresholds(n, "cpu")
+    G = torch.empty(B, 2 * n * w.shape[0], dtype=torch.float64)
+    f = nat.fn(nat.cpu_lib(), "qd_cpu_qsim_mixed_adjoint", [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i])
+    nat.check(f(nat.ptr(x), nat.ptr(w), nat.ptr(thr1), nat.ptr(thr2), nat.ptr(thr_ro), nat.ptr(gE), nat.ptr(G), None,
+                B, n, w.shape[0]), "qd_cpu_qsim_mixed_adjoint")
+    return G
+
+
+def _mixed_adjoint_rows(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, noise: NoiseModel, be: str) -> torch.Tensor:
+    B, n = x.shape
+    if be == "cpu":
+        return _mixed_adjoint_cpu(x, w.contiguous(), gE, noise).float()
+    G = torch.empty(B, 2 * n * w.shape[-3], device=x.device, dtype=torch.float32)
+    if B > 0:
+        hip_qsim_mixed_adjoint(x, w, gE, G, None, noise, wgroup_of(x, w))
+    return G
+
+
+@torch.no_grad()
+def mixed_adjoint_rows(x: torch.Tensor, w: torch.Tensor, gE: torch.Tensor, noise: NoiseModel,
+                       backend: Optional[str] = None) -> torch.Tensor:
+    """``mixed_rows``'s G (B, 2nL) fp32 by reverse-mode differentiation of the channel: the forward recomputed, then
+    rho and the observable carried back through the sweeps, every error site undone on rho (csrc/hip/qsim_mixed.hip
+    qd_qsim_mixed_adjoint in one launch on ``hip``, its complex128 twin on ``cpu``) -- a few forward-equivalents
+    instead of 4 n L.  Undoing a site divides by 1 - 4 p1 / 3 (1 - 16 p2 / 15), so every rate must be <= 0.5; the other
+    refusals are ``mixed_rows``'s."""
+    be = _mixed_backend(x, w, noise, backend)
+    B, n = x.shape
+    if tuple(gE.shape) != (B, n):
+        raise ValueError(f"gE must be ({B}, {n}), got {tuple(gE.shape)}")
+    if gE.device != x.device:
+        raise ValueError(f"gE must be on {x.device}, got {gE.device}")
+    _check_adjoint_rates(noise, n)
+    return _mixed_adjoint_rows(x.detach().float().contiguous(), w.detach().float().contiguous(),
+                               gE.detach().float().contiguous(), noise, be)
+
+
 class _QSimMixed(torch.autograd.Function):
-    """Forward: the exact noisy expectation.  Backward: its exact gradient, ``mixed_rows``."""
+    """Forward: the exact noisy expectation.  Backward: its exact gradient, ``mixed_rows`` or (``adjoint``)
+    ``mixed_adjoint_rows``."""
 
     @staticmethod
-    def forward(ctx, x, w, noise, be):
+    def forward(ctx, x, w, noise, be, adjoint=False):
         x = x.detach().float().contiguous()
         w = w.detach().float().contiguous()
         ctx.save_for_backward(x, w)
-        ctx.args = (noise, be)
+        ctx.args = (noise, be, adjoint)
         return _mixed_fwd(x, w, noise, be).float()
 
     @staticmethod
     def backward(ctx, gE):
         x, w = ctx.saved_tensors
-        noise, be = ctx.args
-        G = _mixed_rows(x, w, gE.detach().float().contiguous(), noise, be)
-        return _rows_to_grads(G, x, w, be) + (None, None)
+        noise, be, adjoint = ctx.args
+        rows = _mixed_adjoint_rows if adjoint else _mixed_rows
+        G = rows(x, w, gE.detach().float().contiguous(), noise, be)
+        return _rows_to_grads(G, x, w, be) + (None, None, None)
 
 
-def qsim_mixed(x: torch.Tensor, w: torch.Tensor, noise: NoiseModel, backend: Optional[str] = None) -> torch.Tensor:
+def qsim_mixed(x: torch.Tensor, w: torch.Tensor, noise: NoiseModel, backend: Optional[str] = None,
+               diff_method: str = "parameter_shift") -> torch.Tensor:
     """<Z_i> (B, n) fp32 of the QSC circuit on the noisy device itself: the expectation that
     ``qsim(x, w, shots=, noise=, trajectories=)`` estimates, with no Monte-Carlo error -- the density matrix evolved
     through the circuit with, in expectation, the Pauli channel the sampling kernels draw from (after wire q's fused
@@ -1332,10 +1424,15 @@ def qsim_mixed(x: torch.Tensor, w: torch.Tensor, noise: NoiseModel, backend: Opt
 
     2 <= n <= 8 (rho has 4^n entries) and 2 n L <= 4096 on both backends: csrc/hip/qsim_mixed.hip on ``hip``, the
     complex128 gate-by-gate oracle of csrc/cpu/qsim_cpu.cpp on ``cpu``; ``torch`` has none.  ``w`` may be grouped as
-    for ``qsim``.  An all-zero ``NoiseModel`` gives the noiseless expectation.  Differentiable in x and w: the
-    backward is ``mixed_rows`` (two forward evaluations per parameter; there is no dedicated adjoint kernel)."""
+    for ``qsim``.  An all-zero ``NoiseModel`` gives the noiseless expectation.  Differentiable in x and w: by default
+    the backward is ``mixed_rows`` (two forward evaluations per parameter); ``diff_method="adjoint"`` makes it
+    ``mixed_adjoint_rows`` (one launch; every gate rate <= 0.5)."""
     be = _mixed_backend(x, w, noise, backend)
-    return _QSimMixed.apply(x, w, noise, be)
+    if diff_method not in MIXED_DIFF_METHODS:
+        raise ValueError(f"qsim_mixed: diff_method must be one of {MIXED_DIFF_METHODS}, got {diff_method!r}")
+    if diff_method == "adjoint":
+        _check_adjoint_rates(noise, x.shape[1])
+    return _QSimMixed.apply(x, w, noise, be, diff_method == "adjoint")
 
 
 def init_weights_(w: torch.Tensor, generator: Optional[torch.Generator] = None) -> torch.Tensor:

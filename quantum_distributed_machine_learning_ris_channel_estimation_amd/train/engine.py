@@ -961,6 +961,8 @@ class ClassifierStep:
                 self._val_calls = getattr(self, "_val_calls", 0) + 1
                 h.infer(self._xin, None, self._logp, shots=h.shots, seed=h.shot_seed,
                         counter=(1 << 40) + self._val_calls - 1, noise=h.noise, trajectories=h.trajectories, valid=n)
+            elif getattr(h, "exact_noise", False):   # the step's device model again: the exact noisy expectation
+                h.infer(self._xin, None, self._logp, noise=h.noise, exact_noise=True, valid=n)
             else:
                 h.infer(self._xin, None, self._logp, valid=n)
             out[lo:lo + n].copy_(self._logp[:n])

@@ -526,10 +526,17 @@ class Y2HRunner:
 
     def qsc_device_knobs(self) -> Optional[Dict]:
         """The QSC_P128 arguments of the qsc_* knobs (diff_method, shots, noise, trajectories), or None with the
-        defaults.  A noise rate needs qsc_shots, as in evaluation; these knobs train at world size 1 only."""
+        defaults.  A noise rate needs qsc_shots, as in evaluation, or qsc_noise_exact (the exact channel, which takes
+        no shots: the dict then carries ``exact_noise``, for the layer and the fused step, not for QSC_P128); these
+        knobs train at world size 1 only."""
         rates = (float(self.qsc_noise_p1), float(self.qsc_noise_p2), float(self.qsc_readout01),
                  float(self.qsc_readout10))
         shots, dm = int(self.qsc_shots), str(self.qsc_diff_method)
+        exact = bool(self.qsc_noise_exact)
+        if exact and shots > 0:
+            raise ValueError("qsc_noise_exact evaluates the noisy device's expectation itself: it needs qsc_shots == 0")
+        if exact and any(rates):
+            return self._qsc_exact_knobs(rates, dm)
         if any(rates) and shots <= 0:
             raise ValueError("qsc_noise_* / qsc_readout* need qsc_shots > 0: the noise model is sampled per shot")
         if dm == "adjoint" and shots <= 0 and int(self.qsc_trajectories) == 1:
@@ -546,6 +553,22 @@ class Y2HRunner:
             raise ValueError("qsc_diff_method / qsc_shots / qsc_noise_* train at world size 1 only")
         return {"diff_method": dm, "shots": shots if shots > 0 else None,
                 "noise": NoiseModel(*rates) if any(rates) else None, "trajectories": int(self.qsc_trajectories)}
+
+    def _qsc_exact_knobs(self, rates, dm: str) -> Dict:
+        """qsc_noise_exact with a rate set: training against the exact expectation of the noisy device
+        (ops/quantum.py qsim_mixed), differentiated by the density-matrix adjoint."""
+        from ..ops.quantum import MIXED_MAX_QUBITS, NoiseModel, _check_adjoint_rates
+        if dm != "adjoint" or int(self.qsc_trajectories) != 1:
+            raise ValueError("qsc_noise_exact differentiates the exact channel by its adjoint: it needs "
+                             "qsc_diff_method=adjoint and qsc_trajectories=1")
+        if int(self.n_qubits) > MIXED_MAX_QUBITS:
+            raise ValueError(f"qsc_noise_exact needs n_qubits <= {MIXED_MAX_QUBITS} (rho has 4^n entries), got "
+                             f"{int(self.n_qubits)}")
+        if self._context().world > 1:
+            raise ValueError("qsc_diff_method / qsc_shots / qsc_noise_* train at world size 1 only")
+        noise = NoiseModel(*rates)
+        _check_adjoint_rates(noise, int(self.n_qubits))
+        return {"diff_method": "adjoint", "shots": None, "noise": noise, "trajectories": 1, "exact_noise": True}
 
     def qsc_post_knobs(self) -> Dict:
         """The QSC_P128 arguments of the qsc_post_* knobs ({} with the defaults).  The normalization's statistics go
@@ -740,15 +763,18 @@ class Y2HRunner:
     def train_QSC_P128(self):
         self._sync_cfg()
         self._context()  # seeds before the model is built
+        knobs = self.qsc_device_knobs()
+        exact = bool(knobs and knobs.get("exact_noise"))   # (the layer's and the fused step's, not the model's)
         model = QSC_P128(self.n_qubits, self.n_layers, self.n_classes, use_quantumnat=self.use_quantumnat,
                          use_gradient_pruning=self.use_gradient_pruning, pilot_num=self.Pilot_num,
                          backend=None if self.backend == "auto" else self.backend, noise_level=self.noise_level,
-                         gradient_threshold=self.gradient_threshold, **(self.qsc_device_knobs() or {}),
-                         **self.qsc_post_knobs())
-        knobs = self.qsc_device_knobs()
+                         gradient_threshold=self.gradient_threshold,
+                         **{k: v for k, v in (knobs or {}).items() if k != "exact_noise"}, **self.qsc_post_knobs())
         on_chip = knobs is not None
         if on_chip:
             model.qlayer.manual_shot_seed(self.seed)   # the shot streams follow the run's seed
+        if exact:   # training and validation under the exact channel, its gradient by the adjoint
+            model.qlayer.exact_noise, model.qlayer.exact_diff_method = True, "adjoint"
         ctx = self._context()
         if str(self.qsc_step) not in ("module", "fused"):
             raise ValueError(f"unknown qsc_step {self.qsc_step!r}: module or fused")
